@@ -16,6 +16,16 @@ partitions per rank + the virtual-node all-reduce.
 A timed step = H2D of the batch + forward + coord-MSE + MMD + backward
 (+ gradient all-reduce, clip and Adam step every 4th step). Compute dtype
 bf16 (autocast) for MLP GEMMs; coordinates/reductions fp32.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the result line. ``--dump-outputs DIR`` additionally writes
+what the last timed step computed (rank 0) as ``DIR/<name>.npy`` so two builds
+can be compared output for output; inputs and initial weights are seeded, so
+they are identical from run to run for the same arguments. ``--full`` is where
+any measurement beyond the headline figure belongs (baselines, other
+precisions or sizes, per-kernel figures); this benchmark has none of its own
+today — the model-family comparison lives in benchmarks/zoo.py — so the flag
+is accepted and changes nothing.
 """
 
 import argparse
@@ -62,11 +72,14 @@ def build_rank_batches(rank, world_size, num_batches, n_nodes, radius,
     return batches
 
 
-def make_step_core(model, accum, mmd_sigma, mmd_samples, autocast_dtype):
+def make_step_core(model, accum, mmd_sigma, mmd_samples, autocast_dtype,
+                   return_preds=False):
     """forward + loss + backward on device-resident batch tensors.
 
     hipGraph-capturable: no host syncs, no collectives (counts_global is
-    reduced eagerly by the caller before the graphed region)."""
+    reduced eagerly by the caller before the graphed region).
+    ``return_preds`` also returns the predicted node and virtual-node
+    coordinates (fp32) after the logged loss (--dump-outputs)."""
 
     def step_core(data):
         # captured collectives (this counts reduce + the in-forward virtual
@@ -100,13 +113,15 @@ def make_step_core(model, accum, mmd_sigma, mmd_samples, autocast_dtype):
                       sample_valid=getattr(data, "mmd_valid", None))
         loss = loss + 0.01 * weight * lm
         (loss / accum).backward()
+        if return_preds:
+            return (mse_log, loc_pred.detach().float(), vloc.detach().float())
         return (mse_log,)
 
     return step_core
 
 
 def train_step(graphed, batch, optimizer, grad_bucket, step, accum,
-               world_size, device, clip=True, mmd_cfg=None):
+               world_size, device, clip=True, mmd_cfg=None, out_sink=None):
     def _pre():
         # eager work between replays (H2D copies included) runs on the side
         # stream: its allocations must not alias captured-graph pool blocks
@@ -120,7 +135,11 @@ def train_step(graphed, batch, optimizer, grad_bucket, step, accum,
         return data
 
     data = graphed.run_eager(_pre)
-    (mse_log,) = graphed(data)
+    outs = graphed(data)
+    mse_log = outs[0]
+    if out_sink is not None:
+        # everything step_core returned, for --dump-outputs
+        out_sink[:] = outs
     if (step + 1) % accum == 0:
         def _opt():
             if grad_bucket is not None:
@@ -170,6 +189,29 @@ def build_cutoff_batches(workload, num_batches, graphs_per_batch, seed):
             for i in range(num_batches)]
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write ``{name: tensor}`` as ``out_dir/<name>.npy`` (float32, or float64
+    where the tensor is), at most DUMP_BUDGET_BYTES in all: an array over its
+    equal share of the budget is cut to a fixed seeded sample of its
+    flattened elements, the same elements in every run."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        a = t.to(torch.float64 if t.dtype == torch.float64
+                 else torch.float32).numpy()
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.random.default_rng(0).choice(a.size, keep, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -203,6 +245,17 @@ def main():
                          "stream allocations between replays alias graph-"
                          "pool blocks on this stack (see "
                          "runtime/graphs.py)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed "
+                         "step computed on rank 0 as DIR/<name>.npy: "
+                         "coord_mse, loc_pred, virtual_loc (the step's "
+                         "returns), grads and params (the state it leaves; "
+                         "grads are those accumulated since the last "
+                         "optimizer step, zeros right after one)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run measurements beyond the headline figure; "
+                         "this benchmark has none today, so a plain run and "
+                         "a --full run do the same work")
     args = ap.parse_args()
 
     rank, world_size = comm.init_distributed()
@@ -258,7 +311,9 @@ def main():
     from distegnn_amd.runtime.graphs import GraphedStep
 
     step_core = make_step_core(model, accum, mmd_sigma, mmd_samples,
-                               autocast_dtype)
+                               autocast_dtype,
+                               return_preds=args.dump_outputs is not None)
+    last_outs = [] if args.dump_outputs is not None else None
     use_graphs = args.graphs != "off"
     graphed = GraphedStep(step_core, model.parameters(),
                           warmup_occurrences=2,
@@ -329,7 +384,8 @@ def main():
     for k in range(args.steps):
         mse = train_step(graphed, batches[k % len(batches)], optimizer,
                          grad_bucket, n_warm + k, accum,
-                         ws_eff, device, clip, mmd_cfg=num_sample)
+                         ws_eff, device, clip, mmd_cfg=num_sample,
+                         out_sink=last_outs)
     if event_timing:
         ev1.record()
         torch.cuda.synchronize()   # safe: no replay runs after this point
@@ -346,6 +402,19 @@ def main():
         torch.distributed.all_reduce(elapsed,
                                      op=torch.distributed.ReduceOp.MAX)
     ms_per_step = elapsed.item() * 1000.0 / args.steps
+
+    # every replay is done and the device is synchronized: D2H reads are safe
+    if last_outs and rank == 0:
+        params = list(model.parameters())
+        dump_outputs(args.dump_outputs, {
+            "coord_mse": last_outs[0],
+            "loc_pred": last_outs[1],
+            "virtual_loc": last_outs[2],
+            "grads": torch.cat([(p.grad if p.grad is not None
+                                 else torch.zeros_like(p)).reshape(-1)
+                                for p in params]),
+            "params": torch.cat([p.detach().reshape(-1) for p in params]),
+        })
 
     # destroy BEFORE printing: RCCL writes a version banner to stdout at
     # teardown, and the driver expects the JSON line to come last. Read the
