@@ -533,8 +533,8 @@ def _warn_fallback(op: str, reason: str):
     print(f"[distegnn_amd.ops] {op}: fused MFMA kernel not applicable "
           f"({reason}); running the eager composition instead — expect a "
           f"large per-step slowdown. The hand-written gfx950 kernels cover "
-          f"hidden_nf in {{32, 64, 128}} (edge; the virtual block needs "
-          f"64), edge_attr_nf=2, virtual_channels<=8, bf16. "
+          f"hidden_nf in {{32, 64, 128}} (edge and virtual blocks), "
+          f"edge_attr_nf=2, virtual_channels<=8, bf16. "
           f"(fp32 evaluation is the reference-parity default and is "
           f"expected to take this path; set train.bf16_eval=true to "
           f"evaluate on the fused bf16 kernels.)",
@@ -619,7 +619,7 @@ class _FusedVirtualBlockFn(torch.autograd.Function):
     """Fused MFMA virtual-edge block (csrc/fused_virtual.hip).
 
     Forward: one kernel over (node, channel) rows builds the virtual-edge
-    inputs in LDS (no [N,C,3]/[N,C,134] torch intermediates) and returns
+    inputs in LDS (no [N,C,3]/[N,C,2H+1+C] torch intermediates) and returns
     per-row messages + head translations; training mode saves the
     pre-activations. Backward: one kernel runs the dz chain from the saved
     pre-activations; python finishes with split-K wgrad GEMMs, bias sums,
@@ -680,10 +680,9 @@ class _FusedVirtualBlockFn(torch.autograd.Function):
         gwxv = chunked_wgrad(dzxv, vmsg).float()
         gwX = chunked_wgrad(dzX, vmsg).float()
         # bias + head-weight grads accumulated in-kernel (LDS + atomics):
-        # avoids four [R,64] column-sum re-reads and two full-tensor silus
-        gb1, gb2 = gb[:64], gb[64:128]
-        gbxv, gbX = gb[128:192], gb[192:256]
-        gwxvv, gwXv = gb[256:320], gb[320:384]
+        # avoids four [R,H] column-sum re-reads and two full-tensor silus
+        hd = z1.size(1)
+        gb1, gb2, gbxv, gbX, gwxvv, gwXv = gb.view(6, hd).unbind(0)
 
         gh = ext.mid_reduce(dh_row.view(n, c, -1), 1.0)
         gcoord = ext.mid_reduce(dvd.view(n, c, 3), -1.0)
@@ -705,13 +704,23 @@ class _FusedVirtualBlockFn(torch.autograd.Function):
                 None)
 
 
+_VIRTUAL_H = (32, 64, 128)   # instantiations in csrc/fused_virtual.hip
+
+
 def fused_virtual_block(h, coord, vcoord, vfeat, gram, batch, ptr, chunks,
                         w1, b1, w2, b2, wxv, bxv, wxvv, wX, bX, wXv):
-    """Dispatch: HIP fused kernel on GPU bf16 H=64 C<=8, eager otherwise.
+    """Dispatch: HIP fused kernel on GPU bf16 with hidden_nf in
+    {32, 64, 128} and virtual_channels <= 8, eager otherwise (one warning
+    names the reason; DISTEGNN_DISABLE_FUSED=1 opts out silently).
+
+    Weight gradients go through ``chunked_wgrad``, whose hand-written
+    split-K kernel covers hidden_nf=64 only; at 32 and 128 they take its
+    torch GEMM path, as the fused edge backward does.
 
     Returns (v_msg [N,C,H], tv [N,C,3], tx [N,C,3]); the model derives
     trans_v = tv.mean(1), agg_v = v_msg.mean(1), and pools tx / v_msg."""
-    usable = (h.is_cuda and h.dtype == torch.bfloat16 and h.size(1) == 64
+    usable = (h.is_cuda and h.dtype == torch.bfloat16
+              and h.size(1) in _VIRTUAL_H
               and vcoord.size(1) <= 8 and ptr is not None
               and hip_ext() is not None
               and os.environ.get("DISTEGNN_DISABLE_FUSED") != "1")
@@ -719,8 +728,9 @@ def fused_virtual_block(h, coord, vcoord, vfeat, gram, batch, ptr, chunks,
             and os.environ.get("DISTEGNN_DISABLE_FUSED") != "1"):
         if h.dtype != torch.bfloat16:
             reason = f"dtype {h.dtype} (kernels are bf16-in/fp32-accum)"
-        elif h.size(1) != 64:
-            reason = f"hidden_nf={h.size(1)} (kernels are compiled for H=64)"
+        elif h.size(1) not in _VIRTUAL_H:
+            reason = (f"hidden_nf={h.size(1)} (the virtual-block kernels are "
+                      f"compiled for H in {{32, 64, 128}})")
         elif vcoord.size(1) > 8:
             reason = f"virtual_channels={vcoord.size(1)} (kernels cover <=8)"
         else:
