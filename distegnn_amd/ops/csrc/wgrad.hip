@@ -189,7 +189,14 @@ torch::Tensor wgrad_splitk_launch(torch::Tensor g, torch::Tensor x) {
   long m = gc.size(0);
   int i_dim = (int)xc.size(1);
   TORCH_CHECK(i_dim <= 208, "wgrad kernel supports I<=208");
+  // no rows: a 0-block grid is an invalid launch and the combine would
+  // divide by its zero chunk length — the gradient of nothing is zero
+  if (m == 0)
+    return torch::zeros({(long)O_DIM, (long)i_dim},
+                        g.options().dtype(torch::kFloat));
   int ip = ((i_dim + 15) / 16) * 16;
+  // tests/test_linear_path_gpu.py (_chunk_len) repeats this formula to put
+  // probe rows on both sides of chunk boundaries — change both together
   long chunk = ((m + 1023) / 1024 + 31) / 32 * 32;  // ~1024 blocks
   if (chunk < 64) chunk = 64;
   long nchunk = (m + chunk - 1) / chunk;

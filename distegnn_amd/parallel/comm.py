@@ -348,10 +348,13 @@ class GradBucket:
         flat = torch.cat([p.data.reshape(-1) for p in self.params])
         dist.broadcast(flat, src=0)
         ofs = 0
-        for p in self.params:
-            n = p.numel()
-            p.data.copy_(flat[ofs:ofs + n].view_as(p))
-            ofs += n
+        # in-place copy on the parameter itself (not .data) so _version
+        # moves and the version-keyed weight cache (ops/prep.py) sees it
+        with torch.no_grad():
+            for p in self.params:
+                n = p.numel()
+                p.copy_(flat[ofs:ofs + n].view_as(p))
+                ofs += n
 
     def prebuild_graph_sync(self):
         """Build the captured grad-sync graph during setup, BEFORE the first
