@@ -51,6 +51,31 @@ def build_rowptr(row: torch.Tensor, num_nodes: int) -> torch.Tensor:
     )
 
 
+def build_chunk_tables(ptr: torch.Tensor, chunk: int = 256):
+    """Host-side chunk tables of the two-stage segmented reduction
+    (``segment_reduce_chunked``): every segment ``[ptr[i], ptr[i+1])`` is
+    cut into spans of at most ``chunk`` rows, in order.
+
+    Returns ``(chunk_begin [K], chunk_end [K], seg_chunk_ptr [B+1])``, all
+    int64 on the CPU; segment i owns chunks ``seg_chunk_ptr[i] ..
+    seg_chunk_ptr[i+1]`` (none for an empty segment).
+
+    256-row chunks: a 113K-node partition yields ~440 chunks -> enough
+    blocks to fill 256 CUs (2048-row chunks left the chip 4/5 idle —
+    measured 416-600 us per pool, 10 ms/step).
+    """
+    offs = [int(v) for v in ptr.tolist()]
+    cb, ce, scp = [], [], [0]
+    for s, e in zip(offs[:-1], offs[1:]):
+        for k in range(s, e, chunk):
+            cb.append(k)
+            ce.append(min(k + chunk, e))
+        scp.append(len(cb))
+    return (torch.tensor(cb, dtype=torch.long),
+            torch.tensor(ce, dtype=torch.long),
+            torch.tensor(scp, dtype=torch.long))
+
+
 class Data:
     """One graph sample. All tensors live on CPU until batched + moved."""
 
@@ -161,20 +186,8 @@ class Batch:
         # hot loop never syncs. See ops/csrc/segment_reduce.hip.
         max_seg = int((self.ptr[1:] - self.ptr[:-1]).max()) if b > 0 else 0
         if max_seg > 4096:
-            # 256-row chunks: a 113K-node partition yields ~440 chunks ->
-            # enough blocks to fill 256 CUs (2048-row chunks left the chip
-            # 4/5 idle — measured 416-600 us per pool, 10 ms/step)
-            chunk = 256
-            cb, ce, scp = [], [], [0]
-            for i in range(b):
-                s, e = int(self.ptr[i]), int(self.ptr[i + 1])
-                for k in range(s, e, chunk):
-                    cb.append(k)
-                    ce.append(min(k + chunk, e))
-                scp.append(len(cb))
-            self.pool_chunk_begin = torch.tensor(cb, dtype=torch.long)
-            self.pool_chunk_end = torch.tensor(ce, dtype=torch.long)
-            self.pool_seg_chunk_ptr = torch.tensor(scp, dtype=torch.long)
+            (self.pool_chunk_begin, self.pool_chunk_end,
+             self.pool_seg_chunk_ptr) = build_chunk_tables(self.ptr)
         else:
             self.pool_chunk_begin = None
             self.pool_chunk_end = None

@@ -402,7 +402,10 @@ def eager_edge_block(h, coord, eattr, row, col, rowptr, colptr, col_perm,
     t1 = F.silu(F.linear(ein, w1, b1))
     msg = F.silu(F.linear(t1, w2, b2))
     p = F.silu(F.linear(msg, w3, b3)) @ w3v
-    trans = cd * p.unsqueeze(-1).float()
+    # p joins cd in at least fp32 (bf16 heads are widened, a float64
+    # reference run is not narrowed)
+    trans = cd * p.unsqueeze(-1).to(
+        torch.promote_types(cd.dtype, torch.float32))
     return msg, trans
 
 

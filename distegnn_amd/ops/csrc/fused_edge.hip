@@ -342,6 +342,13 @@ std::tuple<torch::Tensor, torch::Tensor> fused_edge_forward(
     b1c = prepped[3]; b2c = prepped[4]; b3c = prepped[5]; w3vc = prepped[6];
     TORCH_CHECK(w1p.size(1) == k_pad, "prepped w1p must be row-padded");
   } else {
+    // the kernel reads the weights as bf16: anything else would be
+    // reinterpreted, not converted
+    TORCH_CHECK(w1.scalar_type() == torch::kBFloat16 &&
+                    w2.scalar_type() == torch::kBFloat16 &&
+                    w3.scalar_type() == torch::kBFloat16,
+                "fused_edge_forward: w1/w2/w3 must be bf16 when no prepped "
+                "weights are passed");
     // row-pad W1 to [H][K_PAD] so 16-B B-fragment reads are aligned
     w1p = torch::constant_pad_nd(w1.contiguous(), {0, k_pad - k_in});
     w2c = w2.contiguous();

@@ -702,6 +702,13 @@ static std::vector<torch::Tensor> fused_edge_backward_impl(
     TORCH_CHECK(w1p.size(1) == K_PAD && w1tp.size(0) == K_OUT,
                 "prepped w1p/w1tp must be padded");
   } else {
+    // the kernel reads the weights as bf16: anything else would be
+    // reinterpreted, not converted
+    TORCH_CHECK(w1.scalar_type() == torch::kBFloat16 &&
+                    w2.scalar_type() == torch::kBFloat16 &&
+                    w3.scalar_type() == torch::kBFloat16,
+                "fused_edge_backward: w1/w2/w3 must be bf16 when no prepped "
+                "weights are passed");
     auto w1c = w1.contiguous();
     w1p = torch::constant_pad_nd(w1c, {0, K_PAD - K_IN});
     w1tp = torch::constant_pad_nd(w1c.t().contiguous(),
