@@ -489,11 +489,13 @@ class _FusedEdgeBlockFn(torch.autograd.Function):
                   - ext.segment_reduce_csr_perm(dcd, colptr, col_perm,
                                                 False))
             if not use_wg:
-                from .linear import chunked_wgrad
+                from . import linear as _lin
 
-                gw1 = chunked_wgrad(dz1, ein)[:, :k_in].float()
-                gw2 = chunked_wgrad(dz2, t1).float()
-                gw3 = chunked_wgrad(dz3, msg).float()
+                gw1, gw2, gw3 = _lin.grouped_wgrad(
+                    [(dz1, ein), (dz2, t1), (dz3, msg)])
+                gw1 = gw1[:, :k_in].float()
+                gw2 = gw2.float()
+                gw3 = gw3.float()
             # bias grads accumulated in-kernel (block LDS + atomics):
             # avoids three aten column-sum re-reads of [M, H]
             hd = w1.size(0)
@@ -674,14 +676,16 @@ class _FusedVirtualBlockFn(torch.autograd.Function):
             dtx.reshape(rows, 3).float().contiguous(),
             z1, z2, zxv, zX, p2, w1, w2,
             wxv, wX, wxvv, wXv, prepped)
-        from .linear import chunked_wgrad
+        from . import linear as _lin
 
         k_in = w1.size(1)
         t1 = torch.nn.functional.silu(z1)
-        gw1 = chunked_wgrad(dz1, vin)[:, :k_in].float()
-        gw2 = chunked_wgrad(dz2, t1).float()
-        gwxv = chunked_wgrad(dzxv, vmsg).float()
-        gwX = chunked_wgrad(dzX, vmsg).float()
+        gw1, gw2, gwxv, gwX = _lin.grouped_wgrad(
+            [(dz1, vin), (dz2, t1), (dzxv, vmsg), (dzX, vmsg)])
+        gw1 = gw1[:, :k_in].float()
+        gw2 = gw2.float()
+        gwxv = gwxv.float()
+        gwX = gwX.float()
         # bias + head-weight grads accumulated in-kernel (LDS + atomics):
         # avoids four [R,H] column-sum re-reads and two full-tensor silus
         hd = z1.size(1)

@@ -35,6 +35,9 @@ torch::Tensor cfconv_forward(torch::Tensor xw1, torch::Tensor dist,
                              torch::Tensor offsets, double coeff,
                              double cutoff);
 torch::Tensor wgrad_splitk_launch(torch::Tensor g, torch::Tensor x);
+std::vector<torch::Tensor> wgrad_splitk_group_launch(
+    std::vector<torch::Tensor> gs, std::vector<torch::Tensor> xs);
+std::tuple<int64_t, int64_t, int64_t> wgrad_plan(int64_t m, int64_t i_dim);
 torch::Tensor tall_linear(torch::Tensor x, torch::Tensor bmat,
                           c10::optional<torch::Tensor> bias, int64_t act);
 std::vector<torch::Tensor> fused_virtual_forward(
@@ -124,6 +127,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wgrad_splitk", &wgrad_splitk_launch,
         "split-K MFMA weight gradient: g^T @ x for tall activations",
         py::arg("g"), py::arg("x"));
+  m.def("wgrad_splitk_group", &wgrad_splitk_group_launch,
+        "up to four split-K weight gradients (g_p^T @ x_p) in one call: one "
+        "split-K launch per kernel template, one combine launch; each result "
+        "is bit-equal to wgrad_splitk on the same operands",
+        py::arg("gs"), py::arg("xs"));
+  m.def("wgrad_plan", &wgrad_plan,
+        "split plan of wgrad_splitk for [m, 64] x [m, i_dim]: "
+        "(chunk_rows, n_slabs, round_rows)",
+        py::arg("m"), py::arg("i_dim"));
   m.def("tall_linear", &tall_linear,
         "tall-skinny MFMA linear: act(x @ B^T + bias)",
         py::arg("x"), py::arg("bmat"), py::arg("bias") = c10::nullopt,

@@ -1,16 +1,31 @@
-// Split-K weight-gradient kernel: dW = g^T @ x for tall-skinny activations.
+// Split-K weight-gradient kernels: dW = g^T @ x for tall-skinny activations.
 //
 // Shapes: g [M, 64] bf16 (layer-output grad), x [M, I<=208] bf16
 // (activation), M ~ 10^5..10^6. hipBLASLt's heuristic picks a non-split-K
 // kernel here (6 workgroups on 256 CUs, 2.9 ms measured); torch's bmm
 // split-K workaround costs 2.6 ms of HOST time per call re-running the
-// batched-GEMM heuristic. This kernel owns the shape: each block reduces a
-// row chunk with mfma_f32_16x16x32_bf16 over LDS-transposed sub-tiles and
-// writes an fp32 partial; the [nchunk, 64, I] partials are summed by a
-// tiny torch reduction.
+// batched-GEMM heuristic. These kernels own the shape:
+//
+// * wgrad_splitk: each block reduces one row chunk ("slab") with
+//   mfma_f32_16x16x32_bf16. g and x are staged ROW-MAJOR into LDS with
+//   16-byte stores and the MFMA operands are gathered with the transposed
+//   LDS read ds_read_b64_tr_b16, so there is no hand transpose. LDS is
+//   double-buffered (one barrier per staging round) and two rounds of
+//   global loads are in flight per block (two register sets).
+// * wgrad_combine: ONE launch folds the [n_slabs, 64, IP] fp32 slabs in a
+//   fixed order (16 waves each own a contiguous slab range, then a fixed
+//   16-term fold through LDS) -> run-to-run bit-identical.
+//
+// Both take up to MAX_GROUP problems per launch, described by value in the
+// kernel arguments (safe under hipGraph capture). The split plan
+// (chunk rows, slab count, staging round) is make_plan() below, exported
+// as ext.wgrad_plan so tests and docs read it instead of repeating it.
 
 #include <ATen/hip/HIPContext.h>
 #include <torch/extension.h>
+
+#include <tuple>
+#include <vector>
 
 #include "common.h"
 
@@ -18,67 +33,169 @@ namespace {
 
 constexpr int O_DIM = 64;       // rows of dW (layer width) — fixed
 constexpr int THREADS = 256;    // 4 waves
-// E_STEP: MFMA K per staging round; T_STRIDE = E_STEP + 2 LDS e-stride —
-// (T_STRIDE/2) odd makes the 16 b64 readers of a fragment hit distinct
-// banks. Small-NTW shapes (I=64) are staging-bound and do better with the
-// shorter round; wide shapes (I=144+) amortize staging over 3x the MFMAs.
+constexpr int MAX_GROUP = 4;    // problems per launch
+// Split plan: at most MAX_SLABS slabs (2 blocks per CU), at least
+// MIN_CHUNK rows per slab so the fp32 slab traffic follows M.
+constexpr int MAX_SLABS = 512;
+constexpr int MIN_CHUNK = 448;
+// LDS row strides in bf16 elements. A transposed read takes, per 32-lane
+// half, eight consecutive image rows x 16 B; with a row stride of 8*odd
+// dwords those eight rows start on the eight distinct multiples of 8
+// banks -> conflict-free (degree 1). g: 64 + 16 = 80 elements = 40 dwords;
+// x: IP elements when IP/16 is odd, IP + 16 otherwise (x_stride()).
+constexpr int G_STRIDE = 80;
+constexpr int COMBINE_WAVES = 16;
 
 using bf16 = __hip_bfloat16;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using s16x4 = __attribute__((ext_vector_type(4))) short;
+using s16x8 = __attribute__((ext_vector_type(8))) short;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-// NTW = n-tiles (of 16 cols of x) per wave; ITILES total = waves used * NTW
-// mapping: wave w covers n-tiles [w*NTW, w*NTW+NTW)
-template <int NTW, int E_STEP, int T_STRIDE>
-__global__ __launch_bounds__(THREADS, NTW <= 2 ? 4 : 3) void wgrad_splitk(
-    const bf16* __restrict__ g,  // [M, 64]
-    const bf16* __restrict__ x,  // [M, I]
-    float* __restrict__ part,    // [nchunk, 64, IP] (IP = 16*ceil(I/16))
-    long m, int i_dim, int ip, long chunk) {
+__host__ __device__ inline int x_stride(int ip) {
+  return ((ip >> 4) & 1) ? ip : ip + 16;
+}
+
+struct Problem {
+  const bf16* g;   // [m, 64]
+  const bf16* x;   // [m, i_dim]
+  float* part;     // [n_slabs, 64, ip]
+  long m;
+  long chunk;      // rows per slab, a multiple of the staging round
+  int i_dim;
+  int ip;          // 16 * ceil(i_dim / 16)
+  int block0;      // first block of this problem in the launch
+};
+
+struct Group {
+  Problem p[MAX_GROUP];
+  int n;
+};
+
+struct CombineProblem {
+  const float* part;  // [n_slabs, cols]
+  float* dst;         // [cols]
+  int n_slabs;
+  int block0;
+};
+
+struct CombineGroup {
+  CombineProblem p[MAX_GROUP];
+  int n;
+};
+
+// One transposed read: the 16 lanes of group l>>4 fetch a 4-row x 16-column
+// block; lane 4q+p supplies the address of row q, columns 4p..4p+3, and
+// lane i receives column i with row q in element q.
+__device__ __forceinline__ s16x4 tr_read(const __bf16* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) s16x4*)(p));
+}
+
+// The eight k-values of a lane's MFMA fragment for the 32-row k-step at
+// `p` (the lane's own row/column offset already applied): image rows
+// 4*(l>>4) + {0..3} and 16 + 4*(l>>4) + {0..3}. A and B use the same
+// assignment, so the k order inside the step is permuted identically on
+// both operands. Taking rows 4g.. (not 8g..) makes the two groups of a
+// half read eight CONSECUTIVE rows, which the 8*odd-dword stride spreads
+// over all 64 banks.
+__device__ __forceinline__ bf16x8 tr_frag(const __bf16* p, int stride) {
+  s16x4 lo = tr_read(p);
+  s16x4 hi = tr_read(p + 16 * stride);
+  s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+// NTW = n-tiles (of 16 cols of x) per wave; wave w covers n-tiles
+// [w*NTW, w*NTW+NTW). E_STEP = rows per staging round.
+template <int NTW, int E_STEP>
+__global__ __launch_bounds__(THREADS, NTW <= 2 ? 4 : (NTW == 3 ? 3 : 2)) void
+wgrad_splitk(
+    Group grp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // LDS: gT [64][T_STRIDE] bf16, xT [ip<=208][T_STRIDE] bf16
-  __bf16* gT = reinterpret_cast<__bf16*>(smem);
-  __bf16* xT = gT + O_DIM * T_STRIDE;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int itiles = ip / 16;
+  // wave index as a scalar: the n-tile early-outs below must be
+  // wave-uniform branches, the transposed reads need EXEC all ones
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  long c0 = (long)blockIdx.x * chunk;
-  long c1 = c0 + chunk < m ? c0 + chunk : m;
+  // pick this block's problem with scalar selects (no indexed copy of the
+  // argument struct -> no scratch)
+  const bf16* g = grp.p[0].g;
+  const bf16* x = grp.p[0].x;
+  float* part = grp.p[0].part;
+  long m = grp.p[0].m;
+  long chunk = grp.p[0].chunk;
+  int i_dim = grp.p[0].i_dim;
+  int ip = grp.p[0].ip;
+  int block0 = 0;
+#pragma unroll
+  for (int k = 1; k < MAX_GROUP; ++k) {
+    if (k < grp.n && (int)blockIdx.x >= grp.p[k].block0) {
+      g = grp.p[k].g;
+      x = grp.p[k].x;
+      part = grp.p[k].part;
+      m = grp.p[k].m;
+      chunk = grp.p[k].chunk;
+      i_dim = grp.p[k].i_dim;
+      ip = grp.p[k].ip;
+      block0 = grp.p[k].block0;
+    }
+  }
+  const int slab = (int)blockIdx.x - block0;
+  const int itiles = ip >> 4;
+  const int xs = x_stride(ip);
+  const int cpw = ip >> 3;  // 16-byte chunks per x row
 
-  f32x4 acc[4][NTW] = {};
+  // LDS: two buffers of { G [E_STEP][G_STRIDE], X [E_STEP][xs] } bf16
+  __bf16* lds = reinterpret_cast<__bf16*>(smem);
+  const int buf_elems = E_STEP * (G_STRIDE + xs);
 
-  // Register double-buffering (round 2): the next round's global loads of
-  // g/x are issued DURING the current round's MFMA phase (they have no LDS
-  // dependency), hiding the global latency the old stage->barrier->mfma
-  // sequence exposed every E_STEP rows. Per-thread prefetch registers are
-  // sized by the template's column capacity (ip <= NTW*64).
-  constexpr int GITER = (E_STEP * (O_DIM / 8) + THREADS - 1) / THREADS;
-  constexpr int XITER = (E_STEP * (NTW * 64 / 8) + THREADS - 1) / THREADS;
-  bf16x8 pg[GITER];
-  bf16x8 px[XITER];
+  const long c0 = (long)slab * chunk;
+  const long c1 = c0 + chunk < m ? c0 + chunk : m;
 
-  auto prefetch = [&](long e0) {
-    int ne = (int)((c1 - e0 < E_STEP) ? (c1 - e0) : (long)E_STEP);
+  constexpr int GITER = E_STEP * (O_DIM / 8) / THREADS;
+  constexpr int XITER = (E_STEP * NTW * 8 + THREADS - 1) / THREADS;
+  static_assert(E_STEP * (O_DIM / 8) % THREADS == 0, "g staging is exact");
+
+  // per-thread staging coordinates are the same every round
+  int xe[XITER], xi8[XITER];
+#pragma unroll
+  for (int it = 0; it < XITER; ++it) {
+    int idx = tid + it * THREADS;
+    int e = idx / cpw;
+    xe[it] = e < E_STEP ? e : E_STEP;  // E_STEP = "no chunk for me"
+    xi8[it] = (idx - e * cpw) * 8;
+  }
+
+  struct Regs {
+    bf16x8 g[GITER];
+    bf16x8 x[XITER];
+  };
+
+  // global -> registers; rows at or past c1 (and whole rounds past it)
+  // load nothing and stage zeros
+  auto load = [&](Regs& r, long e0) {
+    long left = c1 - e0;
+    int ne = left < 0 ? 0 : (left < E_STEP ? (int)left : E_STEP);
 #pragma unroll
     for (int it = 0; it < GITER; ++it) {
       int idx = tid + it * THREADS;
-      int e = idx / (O_DIM / 8);
-      int o8 = (idx % (O_DIM / 8)) * 8;
+      int e = idx >> 3;
+      int o8 = (idx & 7) * 8;
       bf16x8 v = {};
-      if (idx < E_STEP * (O_DIM / 8) && e < ne)
+      if (e < ne)
         v = *reinterpret_cast<const bf16x8*>(g + (e0 + e) * O_DIM + o8);
-      pg[it] = v;
+      r.g[it] = v;
     }
 #pragma unroll
     for (int it = 0; it < XITER; ++it) {
-      int idx = tid + it * THREADS;
-      int e = idx / (ip / 8);
-      int i8 = (idx % (ip / 8)) * 8;
+      int e = xe[it];
+      int i8 = xi8[it];
       bf16x8 v = {};
-      if (idx < E_STEP * (ip / 8) && e < ne) {
+      if (e < ne) {
         if (i8 + 8 <= i_dim) {
+          // 16-byte load, only 2-byte aligned when i_dim is odd
           v = *reinterpret_cast<const bf16x8*>(x + (e0 + e) * i_dim + i8);
         } else {
 #pragma unroll
@@ -89,58 +206,78 @@ __global__ __launch_bounds__(THREADS, NTW <= 2 ? 4 : 3) void wgrad_splitk(
           }
         }
       }
-      px[it] = v;
+      r.x[it] = v;
     }
   };
 
-  prefetch(c0);
-  for (long e0 = c0; e0 < c1; e0 += E_STEP) {
-    __syncthreads();
-    // LDS-transpose the prefetched round: gT[o][e], xT[i][e]
+  // registers -> LDS, row-major, one 16-byte store per chunk
+  auto store = [&](const Regs& r, int b) {
+    __bf16* gi = lds + b * buf_elems;
+    __bf16* xi = gi + E_STEP * G_STRIDE;
 #pragma unroll
     for (int it = 0; it < GITER; ++it) {
       int idx = tid + it * THREADS;
-      if (idx >= E_STEP * (O_DIM / 8)) break;
-      int e = idx / (O_DIM / 8);
-      int o8 = (idx % (O_DIM / 8)) * 8;
-      bf16x8 v = pg[it];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) gT[(o8 + u) * T_STRIDE + e] = v[u];
+      *reinterpret_cast<bf16x8*>(gi + (idx >> 3) * G_STRIDE + (idx & 7) * 8) =
+          r.g[it];
     }
 #pragma unroll
     for (int it = 0; it < XITER; ++it) {
-      int idx = tid + it * THREADS;
-      if (idx >= E_STEP * (ip / 8)) break;
-      int e = idx / (ip / 8);
-      int i8 = (idx % (ip / 8)) * 8;
-      bf16x8 v = px[it];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) xT[(i8 + u) * T_STRIDE + e] = v[u];
+      if (xe[it] < E_STEP)
+        *reinterpret_cast<bf16x8*>(xi + xe[it] * xs + xi8[it]) = r.x[it];
     }
-    __syncthreads();
-    if (e0 + E_STEP < c1) prefetch(e0 + E_STEP);
-    // D[o][i] += gT[o][e] * xT[i][e] — A rows = o, B cols = i, K = e
+  };
+
+  f32x4 acc[4][NTW] = {};
+
+  // D[o][i] += G[e][o] * X[e][i] — A rows = o, B cols = i, K = e
+  const int frag_row = 4 * (lane >> 4) + ((lane >> 2) & 3);
+  const int frag_col = 4 * (lane & 3);
+  auto mfma = [&](int b) {
+    const __bf16* gi = lds + b * buf_elems;
+    const __bf16* xi = gi + E_STEP * G_STRIDE;
 #pragma unroll
     for (int kk = 0; kk < E_STEP / 32; ++kk) {
-      int kb = kk * 32 + (lane >> 4) * 8;
+      int row = kk * 32 + frag_row;
+      bf16x8 a[4];
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+        a[mt] = tr_frag(gi + row * G_STRIDE + mt * 16 + frag_col, G_STRIDE);
 #pragma unroll
       for (int nt = 0; nt < NTW; ++nt) {
-        int icol = (wave * NTW + nt) * 16 + (lane & 15);
-        if (wave * NTW + nt >= itiles) break;
-        bf16x8 b = *reinterpret_cast<const bf16x8*>(&xT[icol * T_STRIDE + kb]);
+        if (wave * NTW + nt >= itiles) break;  // wave-uniform
+        bf16x8 bfr =
+            tr_frag(xi + row * xs + (wave * NTW + nt) * 16 + frag_col, xs);
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-          bf16x8 a = *reinterpret_cast<const bf16x8*>(
-              &gT[(mt * 16 + (lane & 15)) * T_STRIDE + kb]);
+        for (int mt = 0; mt < 4; ++mt)
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a, b, acc[mt][nt], 0, 0, 0);
-        }
+              a[mt], bfr, acc[mt][nt], 0, 0, 0);
       }
     }
+  };
+
+  // Round r is staged into buffer r&1. While round r is in its MFMA phase,
+  // the loads of rounds r+1 and r+2 are in flight (register sets rb, ra);
+  // one barrier per round separates a buffer's readers from its next
+  // writers. Plain global loads survive __syncthreads().
+  Regs ra, rb;
+  load(ra, c0);
+  load(rb, c0 + E_STEP);
+  store(ra, 0);
+  load(ra, c0 + 2 * E_STEP);
+  __syncthreads();
+  for (long e0 = c0; e0 < c1; e0 += 2 * E_STEP) {
+    mfma(0);
+    store(rb, 1);
+    load(rb, e0 + 3 * E_STEP);
+    __syncthreads();
+    if (e0 + E_STEP < c1) mfma(1);  // block-uniform
+    store(ra, 0);
+    load(ra, e0 + 4 * E_STEP);
+    __syncthreads();
   }
 
-  // write partial [64][ip]: C layout col=l&15(+16*(w*NTW+nt)), row=(l>>4)*4+r
-  float* out = part + (long)blockIdx.x * O_DIM * ip;
+  // write slab [64][ip]: C layout col=l&15(+16*(w*NTW+nt)), row=(l>>4)*4+r
+  float* out = part + (long)slab * O_DIM * ip;
 #pragma unroll
   for (int nt = 0; nt < NTW; ++nt) {
     if (wave * NTW + nt >= itiles) break;
@@ -156,96 +293,192 @@ __global__ __launch_bounds__(THREADS, NTW <= 2 ? 4 : 3) void wgrad_splitk(
   }
 }
 
-// Row-streaming partial combine: each block owns (row-chunk, col-tile) and
-// sums its rows with coalesced reads; a second pass folds the row-chunk
-// partials. Fixed tree order -> deterministic. aten's sum(0) walks the
-// [nchunk, 64*ip] array column-major (~700 GB/s for this shape).
-__global__ void colsum_rows(const float* __restrict__ src,
-                            float* __restrict__ dst, long rows, long cols,
-                            long rows_per_chunk) {
-  long nchunks = (rows + rows_per_chunk - 1) / rows_per_chunk;
-  long ctiles = (cols + 255) / 256;
-  for (long b = blockIdx.x; b < nchunks * ctiles; b += gridDim.x) {
-    long rc = b / ctiles;
-    long c = (b - rc * ctiles) * 256 + threadIdx.x;
-    if (c >= cols) continue;
-    long r0 = rc * rows_per_chunk;
-    long r1 = r0 + rows_per_chunk < rows ? r0 + rows_per_chunk : rows;
-    float acc = 0.f;
-    for (long r = r0; r < r1; ++r) acc += src[r * cols + c];
-    dst[rc * cols + c] = acc;
+// Slab combine, one launch per call or group. A block owns 128 adjacent
+// columns (one float2 per lane); wave w adds slabs [w*per, (w+1)*per) in
+// ascending order, eight independent loads at a time, and wave 0 folds the
+// 16 wave sums in ascending order. The order depends only on n_slabs.
+__global__ __launch_bounds__(COMBINE_WAVES * 64) void wgrad_combine(
+    CombineGroup grp) {
+  __shared__ float2 fold[COMBINE_WAVES][64];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const float* part = grp.p[0].part;
+  float* dst = grp.p[0].dst;
+  int n_slabs = grp.p[0].n_slabs;
+  int block0 = 0;
+  int next0 = grp.n > 1 ? grp.p[1].block0 : (int)gridDim.x;
+#pragma unroll
+  for (int k = 1; k < MAX_GROUP; ++k) {
+    if (k < grp.n && (int)blockIdx.x >= grp.p[k].block0) {
+      part = grp.p[k].part;
+      dst = grp.p[k].dst;
+      n_slabs = grp.p[k].n_slabs;
+      block0 = grp.p[k].block0;
+      next0 = k + 1 < grp.n ? grp.p[k + 1].block0 : (int)gridDim.x;
+    }
   }
+  // the problem's blocks tile its columns exactly: cols = 128 * nblocks
+  const long cols = 128L * (next0 - block0);
+  const long col = 128L * ((int)blockIdx.x - block0) + 2 * lane;
+  const int per = (n_slabs + COMBINE_WAVES - 1) / COMBINE_WAVES;
+  int s = wave * per;
+  const int s1 = s + per < n_slabs ? s + per : n_slabs;
+  const float* src = part + col;
+  float2 acc = make_float2(0.f, 0.f);
+  for (; s + 8 <= s1; s += 8) {
+    float2 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      v[u] = *reinterpret_cast<const float2*>(src + (long)(s + u) * cols);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      acc.x += v[u].x;
+      acc.y += v[u].y;
+    }
+  }
+  for (; s < s1; ++s) {
+    float2 v = *reinterpret_cast<const float2*>(src + (long)s * cols);
+    acc.x += v.x;
+    acc.y += v.y;
+  }
+  fold[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0) {
+    float2 t = fold[0][lane];
+#pragma unroll
+    for (int w = 1; w < COMBINE_WAVES; ++w) {
+      t.x += fold[w][lane].x;
+      t.y += fold[w][lane].y;
+    }
+    *reinterpret_cast<float2*>(dst + col) = t;
+  }
+}
+
+struct Plan {
+  long chunk;    // rows per slab
+  long n_slabs;
+  int round;     // rows per staging round
+  int ntw;       // kernel template: n-tiles per wave
+  int ip;
+};
+
+// The one place the split is decided. tests/test_wgrad_family_gpu.py reads
+// it through ext.wgrad_plan; the `_chunk_len` of
+// tests/test_linear_path_gpu.py is an older formula that now only supplies
+// probe positions and need not follow this one.
+Plan make_plan(long m, int i_dim) {
+  Plan p;
+  p.ip = ((i_dim + 15) / 16) * 16;
+  p.ntw = (p.ip / 16 + 3) / 4;
+  // the narrow template spends few registers per round: a 64-row round
+  // keeps 2 x 16 KB of loads in flight per block
+  p.round = p.ntw == 1 ? 64 : 32;
+  long chunk = (m + MAX_SLABS - 1) / MAX_SLABS;
+  if (chunk < MIN_CHUNK) chunk = MIN_CHUNK;
+  p.chunk = (chunk + p.round - 1) / p.round * p.round;
+  p.n_slabs = (m + p.chunk - 1) / p.chunk;
+  return p;
+}
+
+template <int NTW, int E_STEP>
+void launch_splitk(const Group& grp, int blocks, int max_ip,
+                   hipStream_t stream) {
+  int smem = 2 * E_STEP * (G_STRIDE + x_stride(max_ip)) * 2;
+  wgrad_splitk<NTW, E_STEP><<<blocks, THREADS, smem, stream>>>(grp);
 }
 
 }  // namespace
 
-torch::Tensor wgrad_splitk_launch(torch::Tensor g, torch::Tensor x) {
-  TORCH_CHECK(g.is_cuda() && g.scalar_type() == torch::kBFloat16,
-              "g must be CUDA bf16");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "x must be bf16");
-  TORCH_CHECK(g.size(1) == O_DIM, "wgrad kernel requires out width 64");
-  auto gc = g.contiguous();
-  auto xc = x.contiguous();
-  long m = gc.size(0);
-  int i_dim = (int)xc.size(1);
-  TORCH_CHECK(i_dim <= 208, "wgrad kernel supports I<=208");
-  // no rows: a 0-block grid is an invalid launch and the combine would
-  // divide by its zero chunk length — the gradient of nothing is zero
-  if (m == 0)
-    return torch::zeros({(long)O_DIM, (long)i_dim},
-                        g.options().dtype(torch::kFloat));
-  int ip = ((i_dim + 15) / 16) * 16;
-  // tests/test_linear_path_gpu.py (_chunk_len) repeats this formula to put
-  // probe rows on both sides of chunk boundaries — change both together
-  long chunk = ((m + 1023) / 1024 + 31) / 32 * 32;  // ~1024 blocks
-  if (chunk < 64) chunk = 64;
-  long nchunk = (m + chunk - 1) / chunk;
-  auto part = torch::empty({nchunk, (long)O_DIM, (long)ip},
-                           g.options().dtype(torch::kFloat));
+std::tuple<int64_t, int64_t, int64_t> wgrad_plan(int64_t m, int64_t i_dim) {
+  TORCH_CHECK(m >= 0 && i_dim >= 1 && i_dim <= 208,
+              "wgrad kernel supports 1<=I<=208");
+  Plan p = make_plan(m, (int)i_dim);
+  return {p.chunk, p.n_slabs, p.round};
+}
+
+std::vector<torch::Tensor> wgrad_splitk_group_launch(
+    std::vector<torch::Tensor> gs, std::vector<torch::Tensor> xs) {
+  const int n = (int)gs.size();
+  TORCH_CHECK(n >= 1 && n <= MAX_GROUP && xs.size() == gs.size(),
+              "wgrad group takes 1..4 (g, x) pairs");
+  std::vector<torch::Tensor> gc(n), xc(n), dw(n);
+  std::vector<Plan> plan(n);
+  long part_elems = 0;
+  for (int k = 0; k < n; ++k) {
+    TORCH_CHECK(gs[k].is_cuda() && gs[k].scalar_type() == torch::kBFloat16,
+                "g must be CUDA bf16");
+    TORCH_CHECK(xs[k].is_cuda() && xs[k].scalar_type() == torch::kBFloat16,
+                "x must be CUDA bf16");
+    TORCH_CHECK(gs[k].dim() == 2 && xs[k].dim() == 2 &&
+                    gs[k].size(0) == xs[k].size(0),
+                "g and x must be [M, 64] and [M, I]");
+    TORCH_CHECK(gs[k].size(1) == O_DIM, "wgrad kernel requires out width 64");
+    TORCH_CHECK(xs[k].size(1) >= 1 && xs[k].size(1) <= 208,
+                "wgrad kernel supports 1<=I<=208");
+    gc[k] = gs[k].contiguous();
+    xc[k] = xs[k].contiguous();
+    plan[k] = make_plan(gc[k].size(0), (int)xc[k].size(1));
+    if (plan[k].n_slabs > 1)
+      part_elems += plan[k].n_slabs * O_DIM * plan[k].ip;
+  }
+  auto f32 = gs[0].options().dtype(torch::kFloat);
   auto stream = at::hip::getCurrentHIPStream();
-  int t_stride = (((i_dim + 15) / 16 + 3) / 4 >= 3) ? 66 : 40;
-  int smem = (O_DIM + ip) * t_stride * 2;
-  int itiles = ip / 16;
-  int ntw = (itiles + 3) / 4;
-  const bf16* gp = reinterpret_cast<const bf16*>(gc.data_ptr());
-  const bf16* xp = reinterpret_cast<const bf16*>(xc.data_ptr());
-  float* pp = part.data_ptr<float>();
-  switch (ntw) {
-    case 1:
-      wgrad_splitk<1, 32, 40><<<(int)nchunk, THREADS, smem, stream>>>(
-          gp, xp, pp, m, i_dim, ip, chunk);
-      break;
-    case 2:
-      wgrad_splitk<2, 32, 40><<<(int)nchunk, THREADS, smem, stream>>>(
-          gp, xp, pp, m, i_dim, ip, chunk);
-      break;
-    case 3:
-      wgrad_splitk<3, 64, 66><<<(int)nchunk, THREADS, smem, stream>>>(
-          gp, xp, pp, m, i_dim, ip, chunk);
-      break;
-    case 4:
-      wgrad_splitk<4, 64, 66><<<(int)nchunk, THREADS, smem, stream>>>(
-          gp, xp, pp, m, i_dim, ip, chunk);
-      break;
-    default:
-      TORCH_CHECK(false, "unsupported I for wgrad kernel");
+  torch::Tensor part;
+  if (part_elems) part = torch::empty({part_elems}, f32);
+
+  Group sk[4];  // one split-K launch per kernel template (ntw 1..4)
+  int sk_blocks[4] = {0, 0, 0, 0};
+  int sk_ip[4] = {0, 0, 0, 0};
+  for (auto& s : sk) s.n = 0;
+  CombineGroup cg;
+  cg.n = 0;
+  int cg_blocks = 0;
+  long part_off = 0;
+  for (int k = 0; k < n; ++k) {
+    const Plan& pl = plan[k];
+    int i_dim = (int)xc[k].size(1);
+    // no rows: a 0-block problem has nothing to launch — the gradient of
+    // nothing is zero
+    if (pl.n_slabs == 0) {
+      dw[k] = torch::zeros({(long)O_DIM, (long)i_dim}, f32);
+      continue;
+    }
+    dw[k] = torch::empty({(long)O_DIM, (long)pl.ip}, f32);
+    float* dst = dw[k].data_ptr<float>();
+    float* slabs = dst;  // a single slab IS the result
+    if (pl.n_slabs > 1) {
+      slabs = part.data_ptr<float>() + part_off;
+      part_off += pl.n_slabs * O_DIM * pl.ip;
+      CombineProblem& c = cg.p[cg.n++];
+      c.part = slabs;
+      c.dst = dst;
+      c.n_slabs = (int)pl.n_slabs;
+      c.block0 = cg_blocks;
+      cg_blocks += O_DIM * pl.ip / 128;
+    }
+    int t = pl.ntw - 1;
+    Problem& p = sk[t].p[sk[t].n++];
+    p.g = reinterpret_cast<const bf16*>(gc[k].data_ptr());
+    p.x = reinterpret_cast<const bf16*>(xc[k].data_ptr());
+    p.part = slabs;
+    p.m = gc[k].size(0);
+    p.chunk = pl.chunk;
+    p.i_dim = i_dim;
+    p.ip = pl.ip;
+    p.block0 = sk_blocks[t];
+    sk_blocks[t] += (int)pl.n_slabs;
+    if (pl.ip > sk_ip[t]) sk_ip[t] = pl.ip;
+    dw[k] = dw[k].narrow(1, 0, i_dim);
   }
-  // two-pass row-streaming combine of the [nchunk, 64*ip] partials
-  long cols = (long)O_DIM * ip;
-  auto dw = torch::empty({(long)O_DIM, (long)ip},
-                         g.options().dtype(torch::kFloat));
-  if (nchunk <= 16) {
-    colsum_rows<<<num_blocks(((cols + 255) / 256) * 256, 256), 256, 0,
-                  stream>>>(pp, dw.data_ptr<float>(), nchunk, cols, nchunk);
-  } else {
-    long rpc = 16;
-    long nmid = (nchunk + rpc - 1) / rpc;
-    auto mid = torch::empty({nmid, cols}, g.options().dtype(torch::kFloat));
-    colsum_rows<<<num_blocks(nmid * ((cols + 255) / 256) * 256, 256), 256, 0,
-                  stream>>>(pp, mid.data_ptr<float>(), nchunk, cols, rpc);
-    colsum_rows<<<num_blocks(((cols + 255) / 256) * 256, 256), 256, 0,
-                  stream>>>(mid.data_ptr<float>(), dw.data_ptr<float>(),
-                            nmid, cols, nmid);
-  }
-  return dw.narrow(1, 0, i_dim);
+  if (sk[0].n) launch_splitk<1, 64>(sk[0], sk_blocks[0], sk_ip[0], stream);
+  if (sk[1].n) launch_splitk<2, 32>(sk[1], sk_blocks[1], sk_ip[1], stream);
+  if (sk[2].n) launch_splitk<3, 32>(sk[2], sk_blocks[2], sk_ip[2], stream);
+  if (sk[3].n) launch_splitk<4, 32>(sk[3], sk_blocks[3], sk_ip[3], stream);
+  if (cg.n)
+    wgrad_combine<<<cg_blocks, COMBINE_WAVES * 64, 0, stream>>>(cg);
+  return dw;
+}
+
+torch::Tensor wgrad_splitk_launch(torch::Tensor g, torch::Tensor x) {
+  return wgrad_splitk_group_launch({g}, {x})[0];
 }

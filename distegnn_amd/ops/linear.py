@@ -52,6 +52,25 @@ def chunked_wgrad(g: torch.Tensor, x: torch.Tensor,
     return out
 
 
+def grouped_wgrad(pairs):
+    """[(g_p, x_p), ...] -> [g_p^T @ x_p, ...] for up to four pairs.
+
+    When every pair fits the split-K kernel (bf16, O=64, I<=208) the whole
+    group is ONE extension call: one split-K launch per kernel template and
+    one combine launch, each result bit-equal to ``chunked_wgrad`` on the
+    same pair. Otherwise every pair goes through ``chunked_wgrad``."""
+    from . import hip_ext
+
+    ext = hip_ext()
+    if (ext is not None and 1 <= len(pairs) <= 4
+            and all(g.is_cuda and g.dtype == torch.bfloat16
+                    and x.dtype == torch.bfloat16 and g.size(1) == 64
+                    and 1 <= x.size(1) <= 208 for g, x in pairs)):
+        return ext.wgrad_splitk_group([g for g, _ in pairs],
+                                      [x for _, x in pairs])
+    return [chunked_wgrad(g, x) for g, x in pairs]
+
+
 def _ext_ok(x, w):
     from . import hip_ext
 
