@@ -59,9 +59,15 @@ class EGCLVel(nn.Module):
     def __init__(self, node_feat_nf, node_feat_out_nf, node_attr_nf,
                  edge_attr_nf, hidden_nf, virtual_channels, world_size,
                  act_fn=None, residual=True, attention=False, normalize=False,
-                 coords_agg="mean", tanh=False, gravity=None):
+                 coords_agg="mean", tanh=False, gravity=None,
+                 skip_feature_update=False):
         super().__init__()
         act_fn = act_fn if act_fn is not None else nn.SiLU()
+        # the layer's h / virtual_feat outputs are discarded by the caller
+        # (FastEGNN's last layer): forward skips agg_v, agg_vf and both
+        # node MLPs and returns the incoming features. Modules and state
+        # dict are the same either way.
+        self.skip_feature_update = skip_feature_update
         self.residual = residual
         self.attention = attention
         self.normalize = normalize
@@ -208,7 +214,14 @@ class EGCLVel(nn.Module):
                 self.coord_mlp_v_virtual[0].weight,
                 self.coord_mlp_v_virtual[0].bias,
                 self.coord_mlp_v_virtual[2].weight.reshape(-1))
-            trans_v = ops.mid_mean(tv)
+            # channel means + graph-mean pools of the block's outputs in
+            # one op (ops.virtual_aggregate)
+            if self.skip_feature_update:
+                trans_v = ops.mid_mean(tv)
+            else:
+                agg_v, trans_v, agg_vf, agg_vc = ops.virtual_aggregate(
+                    v_msg, tv, trans_x, batch, ptr, counts, pool_chunks,
+                    num_graphs=b)
         else:
             vdiff = (ops.gather_rows(virtual_coord, batch, ptr,
                                      chunks=pool_chunks)
@@ -244,25 +257,38 @@ class EGCLVel(nn.Module):
             coord = coord + self.gravity_mlp(h) * self.gravity.to(h.device)
 
         # --- virtual aggregates (fused site B+C collective) -------------
-        agg_vc = ops.graph_mean_pool(
-            trans_x.reshape(n, -1), batch, b, ptr=ptr, counts=counts,
-            chunks=pool_chunks
-        ).reshape(b, c, 3)
-        agg_vf = ops.graph_mean_pool(
-            v_msg.reshape(n, -1), batch, b, ptr=ptr, counts=counts,
-            chunks=pool_chunks
-        ).reshape(b, c, self.hidden_nf)
-        if dist_active:
+        skip = self.skip_feature_update
+        if not vfuse or skip:
+            agg_vc = ops.graph_mean_pool(
+                trans_x.reshape(n, -1), batch, b, ptr=ptr, counts=counts,
+                chunks=pool_chunks
+            ).reshape(b, c, 3)
+        if not vfuse and not skip:
+            agg_vf = ops.graph_mean_pool(
+                v_msg.reshape(n, -1), batch, b, ptr=ptr, counts=counts,
+                chunks=pool_chunks
+            ).reshape(b, c, self.hidden_nf)
+        if dist_active and skip:
+            agg_vc = comm.fused_weighted_average_reduce(
+                [agg_vc], counts, counts_global)
+        elif dist_active:
             agg_vc, agg_vf = comm.fused_weighted_average_reduce(
                 [agg_vc, agg_vf], counts, counts_global)
         virtual_coord = virtual_coord + agg_vc
+        if skip:
+            return h, coord, virtual_feat, virtual_coord
 
         # --- node model, phi_h ------------------------------------------
         if not fuse:
             agg_e = ops.segment_mean(edge_feat, row, n, rowptr=rowptr)
-        agg_v = ops.mid_mean(v_msg)
+        if not vfuse:
+            agg_v = ops.mid_mean(v_msg)
         if node_attr is not None:
-            node_in = torch.cat([h, agg_e, agg_v, node_attr], dim=1)
+            # in h's dtype: an fp32 node_attr would promote the whole
+            # [N, 3H+A] input to fp32 under autocast, only for the Linear
+            # to cast it straight back
+            node_in = torch.cat([h, agg_e, agg_v, node_attr.to(h.dtype)],
+                                dim=1)
         else:
             node_in = torch.cat([h, agg_e, agg_v], dim=1)
         h_out = self.node_mlp(node_in)
@@ -283,7 +309,7 @@ class FastEGNN(nn.Module):
     def __init__(self, node_feat_nf, node_attr_nf, edge_attr_nf, hidden_nf,
                  virtual_channels, world_size, act_fn=None, n_layers=4,
                  residual=True, attention=False, normalize=False, tanh=False,
-                 gravity=None):
+                 gravity=None, skip_dead_update=True):
         super().__init__()
         assert virtual_channels > 0, (
             f"Channels of virtual node must be greater than 0 "
@@ -306,7 +332,11 @@ class FastEGNN(nn.Module):
                         hidden_nf, virtual_channels=virtual_channels,
                         world_size=world_size, act_fn=act_fn,
                         residual=residual, attention=attention,
-                        normalize=normalize, tanh=tanh, gravity=gravity))
+                        normalize=normalize, tanh=tanh, gravity=gravity,
+                        # forward() discards the last layer's h and
+                        # virtual_feat
+                        skip_feature_update=(skip_dead_update
+                                             and i == n_layers - 1)))
 
     def forward(self, node_feat, node_loc, node_vel, loc_mean, edge_index,
                 data_batch, edge_attr=None, node_attr=None, *,

@@ -192,6 +192,65 @@ def mid_mean(x: torch.Tensor) -> torch.Tensor:
     return x.mean(dim=1)
 
 
+class _VirtualAggregateFn(torch.autograd.Function):
+    """Channel means and graph-mean pools of the fused virtual block's
+    outputs (csrc/segment_reduce.hip): one grouped pool launch reads v_msg
+    once for agg_v and agg_vf; one kernel writes all three cotangents."""
+
+    @staticmethod
+    def forward(ctx, v_msg, tv, tx, batch, ptr, cb, ce, scp):
+        ext = _require_ext("virtual_aggregate")
+        ctx.save_for_backward(batch, ptr)
+        agg_v, trans_v, agg_vf, agg_vc = ext.virtual_aggregate_forward(
+            v_msg, tv, tx, ptr, cb, ce, scp)
+        return agg_v, trans_v, agg_vf, agg_vc
+
+    @staticmethod
+    def backward(ctx, dagg_v, dtrans_v, dagg_vf, dagg_vc):
+        batch, ptr = ctx.saved_tensors
+        ext = _require_ext("virtual_aggregate.backward")
+        dvmsg, dtv, dtx = ext.virtual_aggregate_backward(
+            dagg_v.bfloat16(), dtrans_v.float(), dagg_vf.bfloat16(),
+            dagg_vc.float(), batch, ptr)
+        return dvmsg, dtv, dtx, None, None, None, None, None
+
+
+def virtual_aggregate(v_msg: torch.Tensor, tv: torch.Tensor,
+                      tx: torch.Tensor, batch: torch.Tensor,
+                      ptr: Optional[torch.Tensor] = None,
+                      counts: Optional[torch.Tensor] = None,
+                      chunks=None, num_graphs: Optional[int] = None):
+    """Aggregates after the virtual block, from v_msg [N,C,H], tv [N,C,3]
+    and tx [N,C,3]: returns (agg_v [N,H], trans_v [N,3], agg_vf [B,C,H],
+    agg_vc [B,C,3]) = (v_msg.mean(1), tv.mean(1), graph mean of v_msg,
+    graph mean of tx).
+
+    On GPU with bf16 v_msg, fp32 tv/tx and chunk tables this is one fused
+    op each way; otherwise the composition of ``mid_mean`` and
+    ``graph_mean_pool``."""
+    n, c, h = v_msg.shape
+    if (v_msg.is_cuda and hip_ext() is not None and chunks is not None
+            and ptr is not None and ptr.numel() > 1
+            and v_msg.dtype == torch.bfloat16
+            and tv.dtype == torch.float32 and tx.dtype == torch.float32
+            and c <= 8 and h % 8 == 0 and h <= 512 and c * h <= 1024
+            and hasattr(hip_ext(), "virtual_aggregate_forward")):
+        cb, ce, scp = chunks
+        return _VirtualAggregateFn.apply(v_msg, tv, tx, batch, ptr, cb, ce,
+                                         scp)
+    if num_graphs is None:
+        num_graphs = (ptr.numel() - 1 if ptr is not None
+                      else counts.numel())
+    b = num_graphs
+    trans_v = mid_mean(tv)
+    agg_v = mid_mean(v_msg)
+    agg_vc = graph_mean_pool(tx.reshape(n, -1), batch, b, ptr=ptr,
+                             counts=counts, chunks=chunks).reshape(b, c, 3)
+    agg_vf = graph_mean_pool(v_msg.reshape(n, -1), batch, b, ptr=ptr,
+                             counts=counts, chunks=chunks).reshape(b, c, h)
+    return agg_v, trans_v, agg_vf, agg_vc
+
+
 class _CoordUpdateFn(torch.autograd.Function):
     """Fused coordinate-update tail: out = coord + agg + trans_v +
     phi_v * vel (one kernel each way; reference FastEGNN.py:166-188 runs
@@ -703,9 +762,20 @@ class _FusedVirtualBlockFn(torch.autograd.Function):
                 out = ext.segment_reduce_csr(flat.contiguous(), ptr, False)
             return out.view(-1, c, width)
 
-        gvfeat = pool(dvf_row, dvf_row.size(1)).to(ctx.vfeat_dtype)
-        ggram = pool(dgram_row[:, :c].contiguous(), c).float()
-        gvcoord = pool(dvd, 3)
+        if cb.numel():
+            # one stage-1 and one combine launch for the three pools; the
+            # first c columns of dgram_row are read in place
+            gvfeat, ggram, gvcoord = ext.segment_reduce_chunked_group(
+                [dvf_row.view(n, c, -1),
+                 dgram_row.view(n, c, -1)[:, :, :c],
+                 dvd.view(n, c, 3)],
+                ptr, cb, ce, scp, [False, False, False])
+            gvfeat = gvfeat.to(ctx.vfeat_dtype)
+            ggram = ggram.float()
+        else:
+            gvfeat = pool(dvf_row, dvf_row.size(1)).to(ctx.vfeat_dtype)
+            ggram = pool(dgram_row[:, :c].contiguous(), c).float()
+            gvcoord = pool(dvd, 3)
         return (gh, gcoord, gvcoord, gvfeat, ggram, None, None, None, None,
                 None, gw1, gb1, gw2, gb2, gwxv, gbxv, gwxvv, gwX, gbX, gwXv,
                 None)
@@ -770,7 +840,8 @@ def radius_graph(pos: torch.Tensor, r: float, loop: bool = False) -> torch.Tenso
 __all__ = [
     "segment_sum", "segment_mean", "graph_sum_pool", "graph_mean_pool",
     "gather_rows", "fused_edge_block", "eager_edge_block",
-    "fused_virtual_block", "eager_virtual_block", "radius_graph",
+    "fused_virtual_block", "eager_virtual_block", "virtual_aggregate",
+    "mid_mean", "radius_graph",
     "hip_ext", "reference", "refresh_weight_prep", "coord_update",
     "cfconv_msg", "spmm_adj",
 ]

@@ -13,6 +13,17 @@ torch::Tensor segment_reduce_chunked(torch::Tensor data, torch::Tensor rowptr,
                                      torch::Tensor chunk_begin,
                                      torch::Tensor chunk_end,
                                      torch::Tensor seg_chunk_ptr, bool mean);
+std::vector<torch::Tensor> segment_reduce_chunked_group(
+    std::vector<torch::Tensor> tensors, torch::Tensor rowptr,
+    torch::Tensor chunk_begin, torch::Tensor chunk_end,
+    torch::Tensor seg_chunk_ptr, std::vector<bool> means);
+std::vector<torch::Tensor> virtual_aggregate_forward(
+    torch::Tensor v_msg, torch::Tensor tv, torch::Tensor tx,
+    torch::Tensor rowptr, torch::Tensor chunk_begin, torch::Tensor chunk_end,
+    torch::Tensor seg_chunk_ptr);
+std::vector<torch::Tensor> virtual_aggregate_backward(
+    torch::Tensor dagg_v, torch::Tensor dtrans_v, torch::Tensor dagg_vf,
+    torch::Tensor dagg_vc, torch::Tensor batch, torch::Tensor rowptr);
 std::tuple<torch::Tensor, torch::Tensor> radius_graph_gpu(torch::Tensor pos,
                                                           double r);
 std::tuple<torch::Tensor, torch::Tensor> fused_edge_forward(
@@ -94,6 +105,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "two-stage deterministic segmented reduce for huge segments",
         py::arg("data"), py::arg("rowptr"), py::arg("chunk_begin"),
         py::arg("chunk_end"), py::arg("seg_chunk_ptr"), py::arg("mean"));
+  m.def("segment_reduce_chunked_group", &segment_reduce_chunked_group,
+        "segment_reduce_chunked for several operands (contiguous or "
+        "row-strided views) in one stage-1 and one combine launch; each "
+        "result is bit-equal to segment_reduce_chunked on that operand",
+        py::arg("tensors"), py::arg("rowptr"), py::arg("chunk_begin"),
+        py::arg("chunk_end"), py::arg("seg_chunk_ptr"), py::arg("means"));
+  m.def("virtual_aggregate_forward", &virtual_aggregate_forward,
+        "channel means and graph-mean pools of the virtual block outputs: "
+        "{agg_v [N,H], trans_v [N,3], agg_vf [B,C,H], agg_vc [B,C,3]}",
+        py::arg("v_msg"), py::arg("tv"), py::arg("tx"), py::arg("rowptr"),
+        py::arg("chunk_begin"), py::arg("chunk_end"),
+        py::arg("seg_chunk_ptr"));
+  m.def("virtual_aggregate_backward", &virtual_aggregate_backward,
+        "cotangents {dv_msg [N,C,H], dtv [N,C,3], dtx [N,C,3]} of "
+        "virtual_aggregate_forward in one kernel",
+        py::arg("dagg_v"), py::arg("dtrans_v"), py::arg("dagg_vf"),
+        py::arg("dagg_vc"), py::arg("batch"), py::arg("rowptr"));
   m.def("radius_graph_gpu", &radius_graph_gpu,
         "cell-list radius graph -> (edge_index, rowptr)", py::arg("pos"),
         py::arg("r"));

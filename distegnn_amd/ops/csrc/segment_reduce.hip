@@ -12,15 +12,18 @@
 //    threads walk adjacent memory; L2 catches the locality.
 //  * seg_reduce_wave  — F >= 16 (feature aggregation, F=64..320): one wave
 //    per segment, lanes cover features -> fully coalesced 256 B reads/row.
-//  * seg_reduce_chunk + seg_reduce_combine — huge segments (graph pooling:
-//    one segment can be a whole 113K-node partition, B=1): stage 1 reduces
+//  * pool_chunks + pool_combine — huge segments (graph pooling: one
+//    segment can be a whole 113K-node partition, B=1): stage 1 reduces
 //    precomputed row chunks (grid-parallel), stage 2 combines each
-//    segment's chunk partials in order (deterministic). The chunk tables
-//    are built on the HOST at collate time (Batch.ptr is host-known), so
-//    the hot loop has no device->host sync.
+//    segment's chunk partials (both in a fixed order: deterministic), for
+//    up to four operands per launch. The chunk tables are built on the
+//    HOST at collate time (Batch.ptr is host-known), so the hot loop has
+//    no device->host sync.
 
 #include <ATen/hip/HIPContext.h>
 #include <torch/extension.h>
+
+#include <climits>
 
 #include "common.h"
 
@@ -172,122 +175,439 @@ __global__ void seg_reduce_wave4(const T* __restrict__ data,
   }
 }
 
-// stage 1: partial sums over precomputed [chunk_begin, chunk_end) row spans.
-template <typename T>
-__global__ void seg_reduce_chunk(const T* __restrict__ data,
-                                 const long* __restrict__ chunk_begin,
-                                 const long* __restrict__ chunk_end,
-                                 float* __restrict__ partial, long nchunks,
-                                 int f) {
-  long ftiles = (f + blockDim.x - 1) / blockDim.x;
-  for (long b = blockIdx.x; b < nchunks * ftiles; b += gridDim.x) {
-    long c = b / ftiles;
-    int j = (int)(b - c * ftiles) * blockDim.x + threadIdx.x;
-    if (j >= f) continue;
-    long s = chunk_begin[c], e = chunk_end[c];
-    float acc = 0.f;
-    for (long k = s; k < e; ++k) acc += to_f32<T>(data[k * f + j]);
-    partial[c * f + j] = acc;
-  }
+// ---------------------------------------------------------------------------
+// Chunked graph pools (huge segments). Both stages take up to POOL_MAX_OPS
+// operands per launch, described by value in the kernel arguments (safe
+// under hipGraph capture), all sharing one chunk table.
+//
+// Stage 1, one 256-thread block per (operand, chunk): the block is laid
+// out as RL row-lanes x FL feature-lanes with FL = min(nvec, 256) and
+// RL = 256 / FL (nvec = f / V feature vectors of V elements), so f = 320
+// bf16 runs 6 x 40 lanes on 16-byte loads and f = 25 fp32 runs 10 x 25 on
+// scalar loads. Row-lane r adds rows s + r, s + r + RL, ... of the chunk
+// in order into one fp32 accumulator per element; POOL_UNROLL loads are
+// issued per trip before any is consumed. The RL row-lane sums are then
+// folded by a pairwise LDS tree (lane r += lane r + st for st = the
+// largest power of two below RL, halving down to 1). The summation order
+// therefore depends only on the chunk bounds, f and V: not on the grid
+// size, on which operands share the launch, or on timing. No atomics.
+//
+// Stage 2, one block per (operand, segment, COMBINE_FT features): 32
+// chunk-lanes each add every 32nd chunk partial of the segment in order,
+// then the same pairwise LDS tree over the 32 lanes.
+
+constexpr int POOL_THREADS = 256;
+constexpr int POOL_WAVES = POOL_THREADS / WAVE;
+constexpr int POOL_MAX_OPS = 4;
+constexpr int POOL_UNROLL = 8;
+constexpr int COMBINE_FT = 8;   // features per combine block
+constexpr int COMBINE_CL = 32;  // chunk-lanes per combine block
+constexpr int COMBINE_THREADS = COMBINE_CL * COMBINE_FT;
+constexpr int POOL_MID_CMAX = 8;     // channels of a channel-mean rider
+constexpr int POOL_MID_FMAX = 1024;  // C * H of a channel-mean rider
+constexpr int POOL_MID_HMAX = 8 * WAVE;  // H of a bf16 rider: H / 8 lanes
+
+enum PoolKind {
+  POOL_F32_V1 = 0,
+  POOL_F32_V4,
+  POOL_BF16_V1,
+  POOL_BF16_V4,
+  POOL_BF16_V8,
+  POOL_F64_V1,
+};
+
+// A pooled operand is [rows, f] where row n holds f / sub_width sub-rows of
+// sub_width contiguous elements, sub_stride elements apart; rows are
+// row_stride elements apart. A contiguous operand has sub_width = f.
+struct PoolOperand {
+  const void* data;
+  float* partial;   // [nchunks, f] fp32
+  void* out;        // [n, f], operand dtype
+  long row_stride;
+  int sub_stride;
+  int sub_width;
+  int f;
+  int kind;
+  int mean;
+  int tile0;        // first stage-2 tile of this operand
+  // Channel-mean rider (virtual_aggregate): the operand is [rows, C, H]
+  // contiguous and stage 1 also writes mid_out[row, :] = mid_scale *
+  // sum_c data[row, c, :] in the operand dtype. pool == 0 skips the pool.
+  void* mid_out;
+  int mid_c;        // C (0: no rider), at most POOL_MID_CMAX
+  int mid_h;        // H
+  float mid_scale;
+  int pool;
+};
+
+struct PoolGroup {
+  PoolOperand p[POOL_MAX_OPS];
+  int n;
+};
+
+__device__ __forceinline__ float bf16_bits_to_f32(unsigned int hi16) {
+  return __uint_as_float(hi16 << 16);
 }
 
-// small-f path (f <= 16): one WAVE per chunk, FL feature-lanes x RL
-// row-sublanes, fixed-shape shfl_xor tree over the row sublanes
-// (deterministic). Keeps the whole GPU busy for f like 3/15 where a
-// thread-per-output mapping yields only a few thousand threads.
-template <typename T, int FL>
-__global__ void seg_reduce_chunk_small(const T* __restrict__ data,
-                                       const long* __restrict__ chunk_begin,
-                                       const long* __restrict__ chunk_end,
-                                       float* __restrict__ partial,
-                                       long nchunks, int f) {
-  constexpr int RL = WAVE / FL;
-  int lane = threadIdx.x & (WAVE - 1);
-  int rl = lane / FL;
-  int fl = lane % FL;
-  long wave = (blockIdx.x * (long)blockDim.x + threadIdx.x) / WAVE;
-  long nwaves = ((long)gridDim.x * blockDim.x) / WAVE;
-  for (long c = wave; c < nchunks; c += nwaves) {
-    long s = chunk_begin[c], e = chunk_end[c];
-    for (int j = fl; j < f; j += FL) {
-      float acc = 0.f;
-      for (long k = s + rl; k < e; k += RL) acc += to_f32<T>(data[k * f + j]);
+// Same rounding as from_f32<__hip_bfloat16>.
+__device__ __forceinline__ unsigned int f32_to_bf16_bits(float v) {
+  return (unsigned int)__bfloat16_as_ushort(__float2bfloat16(v));
+}
+
+template <int KIND>
+struct PoolLoad;
+
+template <>
+struct PoolLoad<POOL_F32_V1> {
+  static constexpr int V = 1;
+  using Raw = float;
+  static __device__ __forceinline__ Raw load(const void* d, long off) {
+    return reinterpret_cast<const float*>(d)[off];
+  }
+  static __device__ __forceinline__ void add(float* a, Raw r) { a[0] += r; }
+  static __device__ __forceinline__ void store(void* d, long off,
+                                               const float* m) {
+    reinterpret_cast<float*>(d)[off] = m[0];
+  }
+};
+
+template <>
+struct PoolLoad<POOL_F32_V4> {
+  static constexpr int V = 4;
+  using Raw = float4;
+  static __device__ __forceinline__ Raw load(const void* d, long off) {
+    return *reinterpret_cast<const float4*>(
+        reinterpret_cast<const float*>(d) + off);
+  }
+  static __device__ __forceinline__ void add(float* a, Raw r) {
+    a[0] += r.x; a[1] += r.y; a[2] += r.z; a[3] += r.w;
+  }
+};
+
+template <>
+struct PoolLoad<POOL_BF16_V1> {
+  static constexpr int V = 1;
+  using Raw = unsigned short;
+  static __device__ __forceinline__ Raw load(const void* d, long off) {
+    return reinterpret_cast<const unsigned short*>(d)[off];
+  }
+  static __device__ __forceinline__ void add(float* a, Raw r) {
+    a[0] += bf16_bits_to_f32(r);
+  }
+};
+
+template <>
+struct PoolLoad<POOL_BF16_V4> {
+  static constexpr int V = 4;
+  using Raw = uint2;
+  static __device__ __forceinline__ Raw load(const void* d, long off) {
+    return *reinterpret_cast<const uint2*>(
+        reinterpret_cast<const unsigned short*>(d) + off);
+  }
+  static __device__ __forceinline__ void add(float* a, Raw r) {
+    a[0] += bf16_bits_to_f32(r.x & 0xffffu);
+    a[1] += bf16_bits_to_f32(r.x >> 16);
+    a[2] += bf16_bits_to_f32(r.y & 0xffffu);
+    a[3] += bf16_bits_to_f32(r.y >> 16);
+  }
+};
+
+template <>
+struct PoolLoad<POOL_BF16_V8> {
+  static constexpr int V = 8;
+  using Raw = uint4;
+  static __device__ __forceinline__ Raw load(const void* d, long off) {
+    return *reinterpret_cast<const uint4*>(
+        reinterpret_cast<const unsigned short*>(d) + off);
+  }
+  static __device__ __forceinline__ void add(float* a, Raw r) {
+    a[0] += bf16_bits_to_f32(r.x & 0xffffu);
+    a[1] += bf16_bits_to_f32(r.x >> 16);
+    a[2] += bf16_bits_to_f32(r.y & 0xffffu);
+    a[3] += bf16_bits_to_f32(r.y >> 16);
+    a[4] += bf16_bits_to_f32(r.z & 0xffffu);
+    a[5] += bf16_bits_to_f32(r.z >> 16);
+    a[6] += bf16_bits_to_f32(r.w & 0xffffu);
+    a[7] += bf16_bits_to_f32(r.w >> 16);
+  }
+  static __device__ __forceinline__ void store(void* d, long off,
+                                               const float* m) {
+    uint4 w;
+    w.x = f32_to_bf16_bits(m[0]) | (f32_to_bf16_bits(m[1]) << 16);
+    w.y = f32_to_bf16_bits(m[2]) | (f32_to_bf16_bits(m[3]) << 16);
+    w.z = f32_to_bf16_bits(m[4]) | (f32_to_bf16_bits(m[5]) << 16);
+    w.w = f32_to_bf16_bits(m[6]) | (f32_to_bf16_bits(m[7]) << 16);
+    *reinterpret_cast<uint4*>(reinterpret_cast<unsigned short*>(d) + off) = w;
+  }
+};
+
+template <>
+struct PoolLoad<POOL_F64_V1> {
+  static constexpr int V = 1;
+  using Raw = double;
+  static __device__ __forceinline__ Raw load(const void* d, long off) {
+    return reinterpret_cast<const double*>(d)[off];
+  }
+  static __device__ __forceinline__ void add(float* a, Raw r) {
+    a[0] += (float)r;
+  }
+};
+
+// Pairwise LDS tree over `lanes` partial vectors of `width` floats each,
+// laid out red[lane * width + i]; the result lands in lane 0. `lane` is
+// this thread's lane (>= lanes for idle threads), `i0` its first float and
+// V its float count. Every thread of the block must call it.
+template <int V>
+__device__ __forceinline__ void pool_lds_tree(float* red, int lanes, int width,
+                                              int lane, int i0) {
+  int st = 1;
+  while (st < lanes) st <<= 1;
+  for (st >>= 1; st >= 1; st >>= 1) {
+    if (lane < st && lane + st < lanes) {
 #pragma unroll
-      for (int off = FL; off < WAVE; off <<= 1) acc += __shfl_xor(acc, off);
-      if (rl == 0) partial[c * f + j] = acc;
+      for (int i = 0; i < V; ++i)
+        red[lane * width + i0 + i] += red[(lane + st) * width + i0 + i];
+    }
+    __syncthreads();
+  }
+}
+
+template <int KIND>
+__device__ __forceinline__ void pool_chunk_body(const PoolOperand& o, long c,
+                                                long s, long e, float* red) {
+  using L = PoolLoad<KIND>;
+  constexpr int V = L::V;
+  const int nvec = o.f / V;
+  const int FL = nvec < POOL_THREADS ? nvec : POOL_THREADS;
+  const int RL = POOL_THREADS / FL;
+  const int rl = threadIdx.x / FL;
+  const int fl = threadIdx.x - rl * FL;
+  for (int fv0 = 0; fv0 < nvec; fv0 += FL) {
+    const int fv = fv0 + fl;
+    const bool act = rl < RL && fv < nvec;
+    float acc[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) acc[i] = 0.f;
+    if (act) {
+      const int j = fv * V;
+      const int sub = j / o.sub_width;
+      const long foff = (long)sub * o.sub_stride + (j - sub * o.sub_width);
+      for (long k = s + rl; k < e; k += (long)RL * POOL_UNROLL) {
+        typename L::Raw r[POOL_UNROLL];
+#pragma unroll
+        for (int u = 0; u < POOL_UNROLL; ++u) {
+          long row = k + (long)u * RL;
+          row = row < e ? row : k;  // in-bounds stand-in, dropped below
+          r[u] = L::load(o.data, row * o.row_stride + foff);
+        }
+#pragma unroll
+        for (int u = 0; u < POOL_UNROLL; ++u)
+          if (k + (long)u * RL < e) L::add(acc, r[u]);
+      }
+    }
+    float* dst = o.partial + c * o.f + fv * V;
+    if (RL == 1) {
+      if (act) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) dst[i] = acc[i];
+      }
+      continue;
+    }
+    // RL > 1 implies FL == nvec: one trip, every lane's fv is in range
+    const int width = FL * V;
+    __syncthreads();  // the previous item's readers are done with red
+    if (act) {
+#pragma unroll
+      for (int i = 0; i < V; ++i) red[rl * width + fl * V + i] = acc[i];
+    }
+    __syncthreads();
+    pool_lds_tree<V>(red, RL, width, rl, fl * V);
+    if (act && rl == 0) {
+#pragma unroll
+      for (int i = 0; i < V; ++i) dst[i] = red[fl * V + i];
     }
   }
 }
 
-// f % 4 == 0 fast path: thread covers 4 contiguous features (b64 loads for
-// bf16) with two rows unrolled for MLP; same partial layout as above.
-template <typename T>
-__global__ void seg_reduce_chunk4(const T* __restrict__ data,
-                                  const long* __restrict__ chunk_begin,
-                                  const long* __restrict__ chunk_end,
-                                  float* __restrict__ partial, long nchunks,
-                                  int f) {
-  int fquads = f >> 2;
-  long ftiles = (fquads + blockDim.x - 1) / blockDim.x;
-  for (long b = blockIdx.x; b < nchunks * ftiles; b += gridDim.x) {
-    long c = b / ftiles;
-    int fq = (int)(b - c * ftiles) * blockDim.x + threadIdx.x;
-    if (fq >= fquads) continue;
-    long s = chunk_begin[c], e = chunk_end[c];
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
-    long k = s;
-    for (; k + 1 < e; k += 2) {
-      const T* p = data + k * f + fq * 4;
-      const T* q = p + f;
-      a0 += to_f32<T>(p[0]); a1 += to_f32<T>(p[1]);
-      a2 += to_f32<T>(p[2]); a3 += to_f32<T>(p[3]);
-      b0 += to_f32<T>(q[0]); b1 += to_f32<T>(q[1]);
-      b2 += to_f32<T>(q[2]); b3 += to_f32<T>(q[3]);
+// Stage 1 with the channel-mean rider, operand [rows, C, H]: a lane owns
+// V features of H and loops over the C channels, so one pass over the
+// operand yields both the per-row channel mean (fp32 sum over c = 0..C-1 in
+// order, times mid_scale, one rounding: the arithmetic of mid_reduce) and
+// the per-(c, h) pool sums. Lanes are RL row-lanes x FL feature-lanes with
+// FL = H / V rounded up to a power of two. FL must not exceed WAVE, so that
+// every wave holds whole row-lanes (the hosts check H <= POOL_MID_HMAX).
+// Row-lane r adds rows s + r, s + r + RL, ... in order, C loads in flight
+// per row; the row-lanes of a wave are folded by shfl_xor (offsets FL,
+// 2 FL, .. 32), the four waves by a fixed (w0 + w2) + (w1 + w3) through
+// LDS.
+template <int KIND>
+__device__ __forceinline__ void pool_mid_body(const PoolOperand& o, long c,
+                                              long s, long e, float* red,
+                                              bool pool) {
+  using L = PoolLoad<KIND>;
+  constexpr int V = L::V;
+  const int H = o.mid_h, C = o.mid_c;
+  const int nv = H / V;
+  int FL = 1;
+  while (FL < nv) FL <<= 1;
+  const int RL = POOL_THREADS / FL;
+  const int fl = threadIdx.x & (FL - 1);
+  const int rl = threadIdx.x / FL;
+  const bool act = fl < nv;
+  float acc[POOL_MID_CMAX][V];
+#pragma unroll
+  for (int cc = 0; cc < POOL_MID_CMAX; ++cc)
+#pragma unroll
+    for (int i = 0; i < V; ++i) acc[cc][i] = 0.f;
+  if (act) {
+    for (long k = s + rl; k < e; k += RL) {
+      typename L::Raw r[POOL_MID_CMAX];
+      const long base = k * o.row_stride + fl * V;
+#pragma unroll
+      for (int cc = 0; cc < POOL_MID_CMAX; ++cc)
+        if (cc < C) r[cc] = L::load(o.data, base + cc * H);
+      float m[V];
+#pragma unroll
+      for (int i = 0; i < V; ++i) m[i] = 0.f;
+#pragma unroll
+      for (int cc = 0; cc < POOL_MID_CMAX; ++cc)
+        if (cc < C) {
+          L::add(m, r[cc]);
+          L::add(acc[cc], r[cc]);
+        }
+#pragma unroll
+      for (int i = 0; i < V; ++i) m[i] *= o.mid_scale;
+      L::store(o.mid_out, k * H + fl * V, m);
     }
-    if (k < e) {
-      const T* p = data + k * f + fq * 4;
-      a0 += to_f32<T>(p[0]); a1 += to_f32<T>(p[1]);
-      a2 += to_f32<T>(p[2]); a3 += to_f32<T>(p[3]);
+  }
+  if (!pool) return;
+  const int CH = C * H;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  __syncthreads();  // the previous item's readers are done with red
+#pragma unroll
+  for (int cc = 0; cc < POOL_MID_CMAX; ++cc)
+    if (cc < C) {
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        float v = acc[cc][i];
+        for (int off = FL; off < WAVE; off <<= 1) v += __shfl_xor(v, off);
+        if (lane < FL && act) red[wave * CH + cc * H + fl * V + i] = v;
+      }
     }
-    float* o = partial + c * f + fq * 4;
-    o[0] = a0 + b0; o[1] = a1 + b1; o[2] = a2 + b2; o[3] = a3 + b3;
+  __syncthreads();
+  for (int t = threadIdx.x; t < CH; t += POOL_THREADS) {
+    float w[POOL_WAVES];
+#pragma unroll
+    for (int i = 0; i < POOL_WAVES; ++i) w[i] = red[i * CH + t];
+#pragma unroll
+    for (int st = POOL_WAVES / 2; st >= 1; st >>= 1)
+#pragma unroll
+      for (int i = 0; i < st; ++i) w[i] += w[i + st];
+    o.partial[c * CH + t] = w[0];
   }
 }
 
-// stage 2: combine of each segment's chunk partials. Block-parallel: one
-// block per (segment, 32-feature tile); 256 threads = 32 features x 8
-// chunk-lanes, fixed-shape LDS tree over the chunk lanes (deterministic).
-// A 113K-node graph has ~440 chunks and B=1: the old one-thread-per-output
-// loop left the GPU >99% idle (77 us for a 6 MB job).
-template <typename T>
-__global__ void seg_reduce_combine(const float* __restrict__ partial,
-                                   const long* __restrict__ seg_chunk_ptr,
-                                   const long* __restrict__ rowptr,
-                                   T* __restrict__ out, long n, int f,
-                                   bool mean) {
-  __shared__ float red[8][33];
-  long jt = (f + 31) / 32;
-  for (long b = blockIdx.x; b < n * jt; b += gridDim.x) {
-    long seg = b / jt;
-    int j0 = (int)(b - seg * jt) * 32;
-    int jl = threadIdx.x & 31;
-    int j = j0 + jl;
-    int cl = threadIdx.x >> 5;  // chunk lane 0..7
-    long cs = seg_chunk_ptr[seg], ce = seg_chunk_ptr[seg + 1];
+__device__ __forceinline__ PoolOperand pool_pick(const PoolGroup& grp, int k) {
+  PoolOperand o = grp.p[0];
+#pragma unroll
+  for (int i = 1; i < POOL_MAX_OPS; ++i)
+    if (i == k) o = grp.p[i];
+  return o;
+}
+
+// A rider is bf16 with 16-byte loads or fp32 with scalar loads.
+__device__ __forceinline__ void pool_mid_dispatch(const PoolOperand& o, long c,
+                                                  long s, long e, float* red,
+                                                  bool pool) {
+  if (o.kind == POOL_BF16_V8)
+    pool_mid_body<POOL_BF16_V8>(o, c, s, e, red, pool);
+  else
+    pool_mid_body<POOL_F32_V1>(o, c, s, e, red, pool);
+}
+
+__global__ void __launch_bounds__(POOL_THREADS)
+pool_chunks(PoolGroup grp, const long* __restrict__ chunk_begin,
+            const long* __restrict__ chunk_end, long nchunks,
+            const long* __restrict__ rowptr, long nseg, long rows) {
+  __shared__ float red[POOL_WAVES * POOL_MID_FMAX];  // >= POOL_THREADS * 8
+  // Items past the chunks, two per operand: rows before rowptr[0] or from
+  // rowptr[nseg] on are in no segment and no chunk; a rider still owes
+  // their channel means (normally there are none). No pool sums.
+  const long chunk_items = nchunks * grp.n;
+  const long items = chunk_items + 2 * grp.n;
+  for (long b = blockIdx.x; b < items; b += gridDim.x) {
+    const bool extra = b >= chunk_items;  // block-uniform, as all below
+    const long x = b - chunk_items;
+    const int k = extra ? (int)(x >> 1) : (int)(b / nchunks);
+    const long c = extra ? 0 : b - k * nchunks;
+    const PoolOperand o = pool_pick(grp, k);
+    if (extra && !o.mid_c) continue;
+    long s, e;
+    if (!extra) {
+      s = chunk_begin[c];
+      e = chunk_end[c];
+    } else if (x & 1) {
+      s = rowptr[nseg] < 0 ? 0 : rowptr[nseg];
+      e = rows;
+    } else {
+      s = 0;
+      e = rowptr[0] > rows ? rows : rowptr[0];
+    }
+    if (o.mid_c) {
+      pool_mid_dispatch(o, c, s, e, red, !extra && o.pool != 0);
+      continue;
+    }
+    switch (o.kind) {
+      case POOL_F32_V1: pool_chunk_body<POOL_F32_V1>(o, c, s, e, red); break;
+      case POOL_F32_V4: pool_chunk_body<POOL_F32_V4>(o, c, s, e, red); break;
+      case POOL_BF16_V1: pool_chunk_body<POOL_BF16_V1>(o, c, s, e, red); break;
+      case POOL_BF16_V4: pool_chunk_body<POOL_BF16_V4>(o, c, s, e, red); break;
+      case POOL_BF16_V8: pool_chunk_body<POOL_BF16_V8>(o, c, s, e, red); break;
+      default: pool_chunk_body<POOL_F64_V1>(o, c, s, e, red); break;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(COMBINE_THREADS)
+pool_combine(PoolGroup grp, const long* __restrict__ seg_chunk_ptr,
+             const long* __restrict__ rowptr, long n, long tiles) {
+  __shared__ float red[COMBINE_CL * COMBINE_FT];
+  const int jl = threadIdx.x % COMBINE_FT;
+  const int cl = threadIdx.x / COMBINE_FT;
+  for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
+    int k = 0;
+#pragma unroll
+    for (int i = 1; i < POOL_MAX_OPS; ++i)
+      if (i < grp.n && t >= grp.p[i].tile0) k = i;
+    const PoolOperand o = pool_pick(grp, k);
+    const long jt = (o.f + COMBINE_FT - 1) / COMBINE_FT;
+    const long local = t - o.tile0;
+    const long seg = local / jt;
+    const int j = (int)(local - seg * jt) * COMBINE_FT + jl;
+    const long cs = seg_chunk_ptr[seg], ce = seg_chunk_ptr[seg + 1];
     float acc = 0.f;
-    if (j < f)
-      for (long c = cs + cl; c < ce; c += 8) acc += partial[c * f + j];
-    red[cl][jl] = acc;
-    __syncthreads();
-    if (cl == 0 && j < f) {
-      float a = ((red[0][jl] + red[1][jl]) + (red[2][jl] + red[3][jl])) +
-                ((red[4][jl] + red[5][jl]) + (red[6][jl] + red[7][jl]));
-      long len = rowptr[seg + 1] - rowptr[seg];
-      if (mean && len > 0) a /= (float)len;
-      out[seg * f + j] = from_f32<T>(a);
+    if (j < o.f) {
+#pragma unroll 4
+      for (long c = cs + cl; c < ce; c += COMBINE_CL)
+        acc += o.partial[c * o.f + j];
     }
+    __syncthreads();  // the previous tile's readers are done with red
+    red[cl * COMBINE_FT + jl] = acc;
     __syncthreads();
+    pool_lds_tree<1>(red, COMBINE_CL, COMBINE_FT, cl, jl);
+    if (cl == 0 && j < o.f) {
+      float a = red[jl];
+      const long len = rowptr[seg + 1] - rowptr[seg];
+      if (o.mean && len > 0) a /= (float)len;
+      const long oi = seg * o.f + j;
+      if (o.kind == POOL_F64_V1)
+        reinterpret_cast<double*>(o.out)[oi] = (double)a;
+      else if (o.kind >= POOL_BF16_V1)
+        reinterpret_cast<__hip_bfloat16*>(o.out)[oi] = __float2bfloat16(a);
+      else
+        reinterpret_cast<float*>(o.out)[oi] = a;
+    }
   }
 }
 
@@ -418,67 +738,177 @@ torch::Tensor gather_rows_fast(torch::Tensor data, torch::Tensor idx) {
   return out;
 }
 
-torch::Tensor segment_reduce_chunked(torch::Tensor data, torch::Tensor rowptr,
-                                     torch::Tensor chunk_begin,
-                                     torch::Tensor chunk_end,
-                                     torch::Tensor seg_chunk_ptr, bool mean) {
-  TORCH_CHECK(data.is_cuda(), "expected CUDA tensor");
-  auto d = data.contiguous();
+namespace {
+
+bool pool_aligned(const torch::Tensor& t, long row_stride, long sub_stride,
+                  long sub_width, int v) {
+  return sub_width % v == 0 && sub_stride % v == 0 && row_stride % v == 0 &&
+         reinterpret_cast<uintptr_t>(t.data_ptr()) %
+                 (size_t)(v * t.element_size()) == 0;
+}
+
+// Describe `t` ([rows, ...]) as a PoolOperand without copying when its
+// layout allows: contiguous, a row-strided [rows, f], or a [rows, a, w]
+// view with unit stride in w (the first w columns of wider sub-rows).
+// Anything else is made contiguous; `keep` holds what the kernel reads.
+PoolOperand pool_describe(const torch::Tensor& t, torch::Tensor& keep) {
+  keep = t;
+  long f = 1;
+  for (int i = 1; i < t.dim(); ++i) f *= t.size(i);
+  PoolOperand o{};
+  o.f = (int)f;
+  if (f == 0 || t.size(0) == 0) return o;
+  if (t.is_contiguous()) {
+    o.row_stride = f;
+    o.sub_stride = (int)f;
+    o.sub_width = (int)f;
+  } else if (t.dim() == 2 && (t.stride(1) == 1 || t.size(1) == 1) &&
+             t.stride(0) >= f) {
+    o.row_stride = t.stride(0);
+    o.sub_stride = (int)f;
+    o.sub_width = (int)f;
+  } else if (t.dim() == 3 && (t.stride(2) == 1 || t.size(2) == 1) &&
+             t.stride(1) >= t.size(2) &&
+             t.stride(0) >= t.size(1) * t.stride(1) &&
+             t.stride(1) <= INT_MAX) {
+    o.row_stride = t.stride(0);
+    o.sub_stride = (int)t.stride(1);
+    o.sub_width = (int)t.size(2);
+  } else {
+    keep = t.contiguous();
+    o.row_stride = f;
+    o.sub_stride = (int)f;
+    o.sub_width = (int)f;
+  }
+  o.data = keep.data_ptr();
+  auto al = [&](int v) {
+    return pool_aligned(keep, o.row_stride, o.sub_stride, o.sub_width, v);
+  };
+  switch (keep.scalar_type()) {
+    case at::ScalarType::Float:
+      o.kind = al(4) ? POOL_F32_V4 : POOL_F32_V1;
+      break;
+    case at::ScalarType::BFloat16:
+      o.kind = al(8) ? POOL_BF16_V8 : al(4) ? POOL_BF16_V4 : POOL_BF16_V1;
+      break;
+    case at::ScalarType::Double:
+      o.kind = POOL_F64_V1;
+      break;
+    default:
+      TORCH_CHECK(false, "segment_reduce_chunked: unsupported dtype ",
+                  keep.scalar_type());
+  }
+  return o;
+}
+
+// Runs stage 1 and the combine for `ops` (partial / tile0 are filled in
+// here), POOL_MAX_OPS operands per launch pair.
+void pool_launch(std::vector<PoolOperand>& ops, const torch::Tensor& rp,
+                 const torch::Tensor& cb, const torch::Tensor& ce,
+                 const torch::Tensor& scp, const torch::TensorOptions& opt,
+                 long rows) {
+  if (ops.empty()) return;
+  const long n = rp.numel() - 1;
+  const long nchunks = cb.numel();
+  auto stream = at::hip::getCurrentHIPStream();
+  long ftotal = 0;
+  for (auto& o : ops) ftotal += o.pool ? o.f : 0;
+  auto partial = torch::empty({std::max<long>(nchunks * ftotal, 1)},
+                              opt.dtype(torch::kFloat));
+  float* pp = partial.data_ptr<float>();
+  for (size_t i0 = 0; i0 < ops.size(); i0 += POOL_MAX_OPS) {
+    PoolGroup grp{};
+    grp.n = (int)std::min<size_t>(POOL_MAX_OPS, ops.size() - i0);
+    long tiles = 0;
+    bool rider = false;
+    for (int k = 0; k < grp.n; ++k) {
+      PoolOperand& o = ops[i0 + k];
+      rider = rider || o.mid_c > 0;
+      TORCH_CHECK(tiles <= INT_MAX, "segment_reduce_chunked: too large");
+      o.tile0 = (int)tiles;
+      if (o.pool) {
+        o.partial = pp;
+        pp += nchunks * o.f;
+        tiles += n * ((o.f + COMBINE_FT - 1) / COMBINE_FT);
+      }
+      grp.p[k] = o;
+    }
+    if (nchunks > 0 || rider)
+      pool_chunks<<<num_blocks((nchunks + 2) * grp.n, 1),
+                    POOL_THREADS, 0, stream>>>(
+          grp, cb.data_ptr<long>(), ce.data_ptr<long>(), nchunks,
+          rp.data_ptr<long>(), n, rows);
+    if (tiles > 0)
+      pool_combine<<<num_blocks(tiles, 1), COMBINE_THREADS, 0, stream>>>(
+          grp, scp.data_ptr<long>(), rp.data_ptr<long>(), n, tiles);
+  }
+}
+
+void pool_check_tables(const torch::Tensor& rp, const torch::Tensor& cb,
+                       const torch::Tensor& ce, const torch::Tensor& scp) {
+  TORCH_CHECK(rp.is_cuda() && cb.is_cuda() && ce.is_cuda() && scp.is_cuda(),
+              "segment_reduce_chunked: tables must be CUDA tensors");
+  TORCH_CHECK(rp.scalar_type() == torch::kLong &&
+                  cb.scalar_type() == torch::kLong &&
+                  ce.scalar_type() == torch::kLong &&
+                  scp.scalar_type() == torch::kLong,
+              "segment_reduce_chunked: tables must be int64");
+  TORCH_CHECK(ce.numel() == cb.numel() && scp.numel() == rp.numel(),
+              "segment_reduce_chunked: chunk tables do not match ptr");
+}
+
+}  // namespace
+
+// Pools every tensor of `tensors` ([rows, ...] each, same rows) over the
+// ptr-delimited segments with one stage-1 and one combine launch per
+// POOL_MAX_OPS operands. Each result is bit-equal to
+// segment_reduce_chunked on that operand alone.
+std::vector<torch::Tensor> segment_reduce_chunked_group(
+    std::vector<torch::Tensor> tensors, torch::Tensor rowptr,
+    torch::Tensor chunk_begin, torch::Tensor chunk_end,
+    torch::Tensor seg_chunk_ptr, std::vector<bool> means) {
+  TORCH_CHECK(tensors.size() == means.size(),
+              "segment_reduce_chunked_group: one mean flag per tensor");
   auto rp = rowptr.contiguous();
   auto cb = chunk_begin.contiguous();
   auto ce = chunk_end.contiguous();
   auto scp = seg_chunk_ptr.contiguous();
-  long n = rp.numel() - 1;
-  long nchunks = cb.numel();
-  long f = 1;
-  for (int i = 1; i < d.dim(); ++i) f *= d.size(i);
-  std::vector<int64_t> oshape(d.sizes().begin(), d.sizes().end());
-  oshape[0] = n;
-  auto out = torch::empty(oshape, d.options());
-  if (n == 0 || f == 0) return out;
-  auto stream = at::hip::getCurrentHIPStream();
-  auto partial = torch::empty({nchunks, f}, d.options().dtype(torch::kFloat));
+  pool_check_tables(rp, cb, ce, scp);
+  const long n = rp.numel() - 1;
 
-  AT_DISPATCH_FLOATING_TYPES_AND(
-      at::ScalarType::BFloat16, d.scalar_type(), "segment_reduce_chunked",
-      [&] {
-        using T = typename hip_type<scalar_t>::type;
-        const T* dp = reinterpret_cast<const T*>(d.data_ptr());
-        T* op = reinterpret_cast<T*>(out.data_ptr());
-        int threads = 256;
-        if (f <= 4) {
-          seg_reduce_chunk_small<T, 4>
-              <<<num_blocks(nchunks * WAVE, threads), threads, 0, stream>>>(
-                  dp, cb.data_ptr<long>(), ce.data_ptr<long>(),
-                  partial.data_ptr<float>(), nchunks, (int)f);
-        } else if (f <= 16) {
-          seg_reduce_chunk_small<T, 16>
-              <<<num_blocks(nchunks * WAVE, threads), threads, 0, stream>>>(
-                  dp, cb.data_ptr<long>(), ce.data_ptr<long>(),
-                  partial.data_ptr<float>(), nchunks, (int)f);
-        } else if ((f & 3) == 0) {
-          long ftiles = ((f >> 2) + threads - 1) / threads;
-          seg_reduce_chunk4<T><<<num_blocks(nchunks * ftiles, 1), threads, 0,
-                                 stream>>>(dp, cb.data_ptr<long>(),
-                                           ce.data_ptr<long>(),
-                                           partial.data_ptr<float>(),
-                                           nchunks, (int)f);
-        } else {
-          long ftiles = (f + threads - 1) / threads;
-          seg_reduce_chunk<T><<<num_blocks(nchunks * ftiles, 1), threads, 0,
-                                stream>>>(dp, cb.data_ptr<long>(),
-                                          ce.data_ptr<long>(),
-                                          partial.data_ptr<float>(), nchunks,
-                                          (int)f);
-        }
-        long jt = (f + 31) / 32;  // one block per (segment, 32-feat tile)
-        seg_reduce_combine<T><<<num_blocks(n * jt * 256, 256), 256, 0,
-                                stream>>>(partial.data_ptr<float>(),
-                                          scp.data_ptr<long>(),
-                                          rp.data_ptr<long>(), op, n, (int)f,
-                                          mean);
-      });
-  return out;
+  std::vector<torch::Tensor> outs(tensors.size());
+  std::vector<torch::Tensor> keep(tensors.size());
+  std::vector<PoolOperand> ops;
+  for (size_t i = 0; i < tensors.size(); ++i) {
+    const auto& t = tensors[i];
+    TORCH_CHECK(t.is_cuda() && t.dim() >= 1, "expected CUDA tensor");
+    TORCH_CHECK(t.size(0) == tensors[0].size(0),
+                "segment_reduce_chunked_group: row counts differ");
+    PoolOperand o = pool_describe(t, keep[i]);
+    std::vector<int64_t> oshape(t.sizes().begin(), t.sizes().end());
+    oshape[0] = n;
+    outs[i] = torch::empty(oshape, t.options());
+    if (n == 0 || o.f == 0) continue;
+    if (t.size(0) == 0) {  // no rows: every segment is empty
+      outs[i].zero_();
+      continue;
+    }
+    o.out = outs[i].data_ptr();
+    o.mean = means[i] ? 1 : 0;
+    o.pool = 1;
+    ops.push_back(o);
+  }
+  pool_launch(ops, rp, cb, ce, scp, tensors[0].options(),
+              tensors[0].size(0));
+  return outs;
+}
+
+torch::Tensor segment_reduce_chunked(torch::Tensor data, torch::Tensor rowptr,
+                                     torch::Tensor chunk_begin,
+                                     torch::Tensor chunk_end,
+                                     torch::Tensor seg_chunk_ptr, bool mean) {
+  return segment_reduce_chunked_group({data}, rowptr, chunk_begin, chunk_end,
+                                      seg_chunk_ptr, {mean})[0];
 }
 
 namespace {
@@ -555,6 +985,220 @@ torch::Tensor mid_expand(torch::Tensor g, int64_t c, double scale) {
             (float)scale);
       });
   return out;
+}
+
+// ---------------------------------------------------------------------------
+// Aggregates after the fused virtual block (ops.virtual_aggregate).
+//
+// Forward: one grouped pool launch. v_msg [N,C,H] is read once for both
+// its channel mean agg_v [N,H] and its graph-mean pool agg_vf [B,C,H]; tx
+// is pooled to agg_vc [B,C,3] and tv's channel mean trans_v [N,3] rides
+// along (see pool_mid_body). Backward: one elementwise kernel writes
+// dv_msg, dtv and dtx.
+
+namespace {
+
+// dv_msg[n,c,:] = bf16(bf16(dagg_v[n,:] * scale) + bf16(dagg_vf[b,c,:] /
+// bf16(count_b))), b = batch[n]: the roundings of mid_expand, of the bf16
+// divide-and-gather of the pool backward and of autograd's bf16 add, in
+// one pass. dtv[n,c,:] = dtrans_v[n,:] * scale and dtx[n,c,:] =
+// dagg_vc[b,c,:] / float(count_b) are the fp32 halves of the same two
+// backwards. One thread per 8 features of dv_msg (16-byte store), then one
+// per element of dtv/dtx.
+__global__ void virtual_aggregate_bwd_kernel(
+    const unsigned short* __restrict__ dagg_v,   // [N,H] bf16
+    const float* __restrict__ dtrans_v,          // [N,3]
+    const unsigned short* __restrict__ dagg_vf,  // [B,C,H] bf16
+    const float* __restrict__ dagg_vc,           // [B,C,3]
+    const long* __restrict__ batch, const long* __restrict__ ptr,
+    unsigned short* __restrict__ dvmsg, float* __restrict__ dtv,
+    float* __restrict__ dtx, long n, int c, int h, float scale) {
+  const int hq = h >> 3;
+  const int per_node = c * hq;
+  const long nfeat = n * per_node;
+  const long total = nfeat + n * c * 3;
+  for (long o0 = blockIdx.x * (long)blockDim.x; o0 < total;
+       o0 += (long)gridDim.x * blockDim.x) {
+    const long o = o0 + threadIdx.x;
+    if (o >= total) continue;
+    if (o < nfeat) {
+      // one 64-bit division per block trip (uniform), 32-bit ones per lane
+      const long node0 = o0 / per_node;
+      const unsigned int t = (unsigned int)(o0 - node0 * per_node) + threadIdx.x;
+      const unsigned int dn = t / (unsigned int)per_node;
+      const unsigned int within = t - dn * (unsigned int)per_node;
+      const int cc = (int)(within / (unsigned int)hq);
+      const int q = (int)(within - (unsigned int)cc * (unsigned int)hq);
+      const long node = node0 + dn;
+      const long b = batch[node];
+      long len = ptr[b + 1] - ptr[b];
+      if (len < 1) len = 1;
+      const float cnt = bf16_bits_to_f32(f32_to_bf16_bits((float)len));
+      const uint4 a =
+          *reinterpret_cast<const uint4*>(dagg_v + node * h + q * 8);
+      const uint4 g = *reinterpret_cast<const uint4*>(
+          dagg_vf + (b * c + cc) * (long)h + q * 8);
+      const unsigned int aw[4] = {a.x, a.y, a.z, a.w};
+      const unsigned int gw[4] = {g.x, g.y, g.z, g.w};
+      unsigned int ow[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        unsigned int half[2];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          const unsigned int ab = p ? aw[i] >> 16 : aw[i] & 0xffffu;
+          const unsigned int gb = p ? gw[i] >> 16 : gw[i] & 0xffffu;
+          const float x =
+              bf16_bits_to_f32(f32_to_bf16_bits(bf16_bits_to_f32(ab) * scale));
+          const float y =
+              bf16_bits_to_f32(f32_to_bf16_bits(bf16_bits_to_f32(gb) / cnt));
+          half[p] = f32_to_bf16_bits(x + y);
+        }
+        ow[i] = half[0] | (half[1] << 16);
+      }
+      *reinterpret_cast<uint4*>(dvmsg + o * 8) =
+          make_uint4(ow[0], ow[1], ow[2], ow[3]);
+    } else {
+      const long t = o - nfeat;
+      const int c3 = c * 3;
+      const long base0 = o0 > nfeat ? o0 - nfeat : 0;  // uniform
+      const long node0 = base0 / c3;
+      const unsigned int u = (unsigned int)(t - node0 * c3);
+      const unsigned int dn = u / (unsigned int)c3;
+      const unsigned int within = u - dn * (unsigned int)c3;
+      const int cc = (int)(within / 3u);
+      const int j = (int)(within - (unsigned int)cc * 3u);
+      const long node = node0 + dn;
+      const long b = batch[node];
+      long len = ptr[b + 1] - ptr[b];
+      if (len < 1) len = 1;
+      dtv[t] = dtrans_v[node * 3 + j] * scale;
+      dtx[t] = dagg_vc[(b * c + cc) * 3 + j] / (float)len;
+    }
+  }
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> virtual_aggregate_forward(
+    torch::Tensor v_msg, torch::Tensor tv, torch::Tensor tx,
+    torch::Tensor rowptr, torch::Tensor chunk_begin, torch::Tensor chunk_end,
+    torch::Tensor seg_chunk_ptr) {
+  TORCH_CHECK(v_msg.is_cuda() && v_msg.dim() == 3 &&
+                  v_msg.scalar_type() == at::ScalarType::BFloat16,
+              "virtual_aggregate: v_msg must be [N,C,H] CUDA bf16");
+  const long nn = v_msg.size(0), c = v_msg.size(1), h = v_msg.size(2);
+  TORCH_CHECK(c >= 1 && c <= POOL_MID_CMAX && h % 8 == 0 &&
+                  h <= POOL_MID_HMAX && c * h <= POOL_MID_FMAX,
+              "virtual_aggregate: needs C <= 8, H % 8 == 0, H <= 512, "
+              "C*H <= 1024");
+  auto chk3 = [&](const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.dim() == 3 && t.size(0) == nn &&
+                    t.size(1) == c && t.size(2) == 3 &&
+                    t.scalar_type() == at::ScalarType::Float,
+                "virtual_aggregate: ", name, " must be [N,C,3] CUDA fp32");
+  };
+  chk3(tv, "tv");
+  chk3(tx, "tx");
+  auto vm = v_msg.contiguous();
+  auto tvc = tv.contiguous();
+  auto txc = tx.contiguous();
+  auto rp = rowptr.contiguous();
+  auto cb = chunk_begin.contiguous();
+  auto ce = chunk_end.contiguous();
+  auto scp = seg_chunk_ptr.contiguous();
+  pool_check_tables(rp, cb, ce, scp);
+  const long n = rp.numel() - 1;
+  // agg_v / trans_v cover all N rows, also those outside every segment
+  auto agg_v = torch::empty({nn, h}, vm.options());
+  auto trans_v = torch::empty({nn, 3}, tvc.options());
+  auto agg_vf = torch::empty({n, c, h}, vm.options());
+  auto agg_vc = torch::empty({n, c, 3}, txc.options());
+  if (nn == 0) {
+    agg_vf.zero_();
+    agg_vc.zero_();
+    return {agg_v, trans_v, agg_vf, agg_vc};
+  }
+  const float scale = (float)(1.0 / (double)c);
+  std::vector<PoolOperand> ops(3);
+  PoolOperand& a = ops[0];  // v_msg: channel mean + pool
+  a.data = vm.data_ptr();
+  a.out = agg_vf.data_ptr();
+  a.row_stride = c * h;
+  a.sub_stride = a.sub_width = a.f = (int)(c * h);
+  a.kind = POOL_BF16_V8;
+  a.mean = 1;
+  a.pool = 1;
+  a.mid_out = agg_v.data_ptr();
+  a.mid_c = (int)c;
+  a.mid_h = (int)h;
+  a.mid_scale = scale;
+  PoolOperand& x = ops[1];  // tx: pool only
+  x.data = txc.data_ptr();
+  x.out = agg_vc.data_ptr();
+  x.row_stride = c * 3;
+  x.sub_stride = x.sub_width = x.f = (int)(c * 3);
+  x.kind = POOL_F32_V1;
+  x.mean = 1;
+  x.pool = 1;
+  PoolOperand& v = ops[2];  // tv: channel mean only
+  v.data = tvc.data_ptr();
+  v.row_stride = c * 3;
+  v.sub_stride = v.sub_width = v.f = (int)(c * 3);
+  v.kind = POOL_F32_V1;
+  v.pool = 0;
+  v.mid_out = trans_v.data_ptr();
+  v.mid_c = (int)c;
+  v.mid_h = 3;
+  v.mid_scale = scale;
+  pool_launch(ops, rp, cb, ce, scp, vm.options(), nn);
+  return {agg_v, trans_v, agg_vf, agg_vc};
+}
+
+std::vector<torch::Tensor> virtual_aggregate_backward(
+    torch::Tensor dagg_v, torch::Tensor dtrans_v, torch::Tensor dagg_vf,
+    torch::Tensor dagg_vc, torch::Tensor batch, torch::Tensor rowptr) {
+  TORCH_CHECK(dagg_v.is_cuda() && dagg_v.dim() == 2 && dagg_vf.dim() == 3 &&
+                  dagg_v.scalar_type() == at::ScalarType::BFloat16 &&
+                  dagg_vf.scalar_type() == at::ScalarType::BFloat16,
+              "virtual_aggregate backward: dagg_v [N,H], dagg_vf [B,C,H] bf16");
+  const long n = dagg_v.size(0), h = dagg_v.size(1);
+  const long nb = dagg_vf.size(0), c = dagg_vf.size(1);
+  TORCH_CHECK(h % 8 == 0 && dagg_vf.size(2) == h && c >= 1,
+              "virtual_aggregate backward: H % 8 == 0 and matching H");
+  TORCH_CHECK(dtrans_v.scalar_type() == at::ScalarType::Float &&
+                  dagg_vc.scalar_type() == at::ScalarType::Float &&
+                  dtrans_v.dim() == 2 && dtrans_v.size(0) == n &&
+                  dtrans_v.size(1) == 3 && dagg_vc.dim() == 3 &&
+                  dagg_vc.size(0) == nb && dagg_vc.size(1) == c &&
+                  dagg_vc.size(2) == 3,
+              "virtual_aggregate backward: dtrans_v [N,3], dagg_vc [B,C,3] "
+              "fp32");
+  TORCH_CHECK(batch.scalar_type() == torch::kLong && batch.numel() == n &&
+                  rowptr.scalar_type() == torch::kLong &&
+                  rowptr.numel() == nb + 1,
+              "virtual_aggregate backward: batch [N], ptr [B+1] int64");
+  auto dav = dagg_v.contiguous();
+  auto dtr = dtrans_v.contiguous();
+  auto dvf = dagg_vf.contiguous();
+  auto dvc = dagg_vc.contiguous();
+  auto bt = batch.contiguous();
+  auto rp = rowptr.contiguous();
+  auto dvmsg = torch::empty({n, c, h}, dav.options());
+  auto dtv = torch::empty({n, c, 3}, dtr.options());
+  auto dtx = torch::empty({n, c, 3}, dtr.options());
+  if (n == 0) return {dvmsg, dtv, dtx};
+  auto stream = at::hip::getCurrentHIPStream();
+  const long total = n * c * (h / 8) + n * c * 3;
+  virtual_aggregate_bwd_kernel<<<num_blocks(total, 256), 256, 0, stream>>>(
+      reinterpret_cast<const unsigned short*>(dav.data_ptr()),
+      dtr.data_ptr<float>(),
+      reinterpret_cast<const unsigned short*>(dvf.data_ptr()),
+      dvc.data_ptr<float>(), bt.data_ptr<long>(), rp.data_ptr<long>(),
+      reinterpret_cast<unsigned short*>(dvmsg.data_ptr()),
+      dtv.data_ptr<float>(), dtx.data_ptr<float>(), n, (int)c, (int)h,
+      (float)(1.0 / (double)c));
+  return {dvmsg, dtv, dtx};
 }
 
 // ---------------------------------------------------------------------------
