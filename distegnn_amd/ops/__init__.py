@@ -531,6 +531,17 @@ class _FusedEdgeBlockFn(torch.autograd.Function):
                       and h.size(1) == 64
                       and os.environ.get("DISTEGNN_EDGE_WGRAD_FUSED",
                                          "0") == "1")
+            # Default: the node-sum path. z1 is linear in ein and ein is
+            # a gather of node rows, so dh and the h-columns of dW1 follow
+            # from S_row/S_col, the per-node sums of dz1 (docs/KERNELS.md):
+            # the kernel stores no ein/dh_row/dh_col and the 1.65M-row
+            # I=144 wgrad becomes N-row products. The per-edge path stays
+            # behind DISTEGNN_EDGE_BWD_PER_EDGE=1 for A/B and accuracy runs.
+            use_lin = (not use_wg and os.environ.get(
+                "DISTEGNN_EDGE_BWD_PER_EDGE", "0") != "1")
+            if use_lin:
+                return _edge_backward_lin(ext, args, h, rowptr, colptr,
+                                          col_perm, w1)
             if use_wg:
                 # weight gradients accumulated IN the backward kernel (MFMA
                 # accumulators): no [M,144]/[M,64] per-edge intermediates,
@@ -581,6 +592,49 @@ class _FusedEdgeBlockFn(torch.autograd.Function):
         gh, gc, gw1, gb1, gw2, gb2, gw3, gb3, gw3v = grads
         return (gh, gc, None, None, None, None, None, None,
                 gw1, gb1, gw2, gb2, gw3, gb3, gw3v, None, None)
+
+
+def _edge_backward_lin(ext, args, h, rowptr, colptr, col_perm, w1):
+    """Edge-block backward from per-node sums of dz1 (the default path).
+
+    S_row/S_col are fp32 sums of bf16 rows; each leaves the CSR reduction
+    as two bf16 halves (hi = bf16(S), lo = bf16(S - hi)). One [2N,2H]
+    buffer holds [S_row | S_col] hi in rows 0..N-1 and lo in rows N..2N-1.
+    gh is one tall_linear over the hi rows; the h-columns of dW1 are
+    h^T @ hi + h^T @ lo = [h; h]^T @ [hi; lo], ONE member of the grouped
+    split-K call next to dW2 and dW3 (the sum over hi and lo happens in
+    the kernel's fp32 accumulators). Nothing here uses atomics on a weight
+    gradient: dW1, dW2 and dW3 are bit-identical run to run."""
+    import torch.nn.functional as F
+
+    from . import linear as _lin
+    from . import prep
+
+    hd = h.size(1)
+    n = rowptr.numel() - 1
+    (t1, msg, dz1, dz2, dz3, dcd, gw3v, gb,
+     gw1_tail) = ext.fused_edge_backward_lin(*args)
+    s = torch.empty((2 * n, 2 * hd), dtype=torch.bfloat16, device=h.device)
+    s_hi, s_lo = s[:n], s[n:]
+    ext.segment_reduce_csr_split(dz1, rowptr, None,
+                                 s_hi[:, :hd], s_lo[:, :hd])
+    ext.segment_reduce_csr_split(dz1, colptr, col_perm,
+                                 s_hi[:, hd:], s_lo[:, hd:])
+    w_hh = prep.get(w1, "hh_t")
+    if _lin._ext_ok(s_hi, w_hh):
+        gh = ext.tall_linear(s_hi, w_hh, None, 0)
+    else:   # 2H past the tall_linear width (H=128)
+        gh = F.linear(s_hi, w_hh)
+    gc = (ext.segment_reduce_csr(dcd, rowptr, False)
+          - ext.segment_reduce_csr_perm(dcd, colptr, col_perm, False))
+    # h^T @ [S_row | S_col] = [(S_row^T h)^T | (S_col^T h)^T]
+    a, gw2, gw3 = _lin.grouped_wgrad(
+        [(torch.cat([h, h]), s), (dz2, t1), (dz3, msg)])
+    a = a.float()
+    gw1 = torch.cat([a[:, :hd].t(), a[:, hd:].t(), gw1_tail], dim=1)
+    gb1, gb2, gb3 = gb[:hd], gb[hd:2 * hd], gb[2 * hd:]
+    return (gh.to(h.dtype), gc, None, None, None, None, None, None,
+            gw1, gb1, gw2.float(), gb2, gw3.float(), gb3, gw3v, None, None)
 
 
 _FALLBACK_WARNED = set()

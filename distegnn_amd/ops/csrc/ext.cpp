@@ -79,6 +79,17 @@ std::vector<torch::Tensor> fused_edge_backward_wg(
     torch::Tensor w2, torch::Tensor b2, torch::Tensor w3, torch::Tensor b3,
     torch::Tensor w3v, bool normalize, double eps,
     std::vector<torch::Tensor> prepped = {});
+std::vector<torch::Tensor> fused_edge_backward_lin(
+    torch::Tensor h, torch::Tensor coord, torch::Tensor eattr,
+    torch::Tensor row, torch::Tensor col, torch::Tensor dmsg_n,
+    torch::Tensor dtrans_n, torch::Tensor w1, torch::Tensor b1,
+    torch::Tensor w2, torch::Tensor b2, torch::Tensor w3, torch::Tensor b3,
+    torch::Tensor w3v, bool normalize, double eps,
+    std::vector<torch::Tensor> prepped = {});
+std::vector<torch::Tensor> segment_reduce_csr_split(
+    torch::Tensor data, torch::Tensor rowptr,
+    c10::optional<torch::Tensor> perm, c10::optional<torch::Tensor> hi_out,
+    c10::optional<torch::Tensor> lo_out);
 
 torch::Tensor radius_graph(torch::Tensor pos, double r) {
   return std::get<0>(radius_graph_gpu(pos, r));
@@ -152,6 +163,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w3"), py::arg("b3"), py::arg("w3v"), py::arg("normalize"),
         py::arg("eps"),
         py::arg("prepped") = std::vector<torch::Tensor>{});
+  m.def("fused_edge_backward_lin", &fused_edge_backward_lin,
+        "edge-block backward for the node-sum path: no ein, dh_row or "
+        "dh_col; {t1, msg, dz1, dz2, dz3, dcd, dw3v, gb, gw1_tail [H,3]}",
+        py::arg("h"), py::arg("coord"), py::arg("eattr"), py::arg("row"),
+        py::arg("col"), py::arg("dmsg_n"), py::arg("dtrans_n"),
+        py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"),
+        py::arg("w3"), py::arg("b3"), py::arg("w3v"), py::arg("normalize"),
+        py::arg("eps"),
+        py::arg("prepped") = std::vector<torch::Tensor>{});
+  m.def("segment_reduce_csr_split", &segment_reduce_csr_split,
+        "CSR segmented sum of bf16 rows (optionally data[perm[k]]) whose "
+        "fp32 result is emitted as two bf16 halves: hi = bf16(S), bit-equal "
+        "to segment_reduce_csr, and lo = bf16(S - hi). hi_out / lo_out may "
+        "be [n, f] column slices of wider buffers",
+        py::arg("data"), py::arg("rowptr"), py::arg("perm") = c10::nullopt,
+        py::arg("hi_out") = c10::nullopt, py::arg("lo_out") = c10::nullopt);
   m.def("wgrad_splitk", &wgrad_splitk_launch,
         "split-K MFMA weight gradient: g^T @ x for tall activations",
         py::arg("g"), py::arg("x"));

@@ -4,6 +4,8 @@
 // every per-edge gradient in ONE kernel. See fused_edge.hip for the chain;
 // the python side finishes with three split-K wgrad GEMMs, bias column
 // sums and CSR segment sums (ops/__init__.py _FusedEdgeBlockFn.backward).
+// The default mode, EB_LIN below, leaves dh and the h-columns of dW1 to
+// per-node sums of dz1 and emits neither ein nor dh_row / dh_col.
 //
 // Occupancy design (PMC-driven, same as the forward): weights are read
 // from GLOBAL padded/transposed copies (L2-resident) instead of LDS, and
@@ -192,9 +194,24 @@ __builtin_amdgcn_s_setprio(1);
 // the split-K wgrad kernels re-reading them). Costs 68 persistent
 // VGPRs -> 2 waves/SIMD instead of 3; saves the whole wgrad kernel
 // family plus the traffic.
-template <int H, bool FUSE_WG>
+//
+// EB_LIN: the first layer is linear in ein and ein is a gather of node
+// rows, so dh and the h-columns of dW1 follow from per-node sums of dz1
+// (S_row, S_col; see docs/KERNELS.md). This mode stores neither ein nor
+// dh_row/dh_col and computes only the dein n-tile that holds column 2H
+// (dr2, which dcd needs). The three dW1 columns that are per-edge (r2 and
+// the two edge attributes) are formed here, in the column loop that sums
+// gb1: dz1 times the bf16 values in columns 2H..2H+2 of in_tile, summed
+// over a wave's 16 rows in a fixed order and stored as one partial row per
+// (tile, wave). The host folds the partial rows with a deterministic sum,
+// so dW1 is bit-identical run to run (no atomics on a weight gradient).
+enum EdgeBwdMode { EB_PLAIN = 0, EB_FUSE_WG = 1, EB_LIN = 2 };
+
+template <int H, int MODE>
 __global__ __launch_bounds__(THREADS,
-                             FUSE_WG ? 2 : (H <= 64 ? 3 : 1))
+                             MODE == EB_FUSE_WG ? 2
+                             : (MODE == EB_LIN && H == 32) ? 4
+                             : (H <= 64 ? 3 : 1))
 void fused_edge_bwd(
     const bf16* __restrict__ h, const float* __restrict__ coord,
     const float* __restrict__ eattr, const long* __restrict__ row,
@@ -213,10 +230,13 @@ void fused_edge_bwd(
     bf16* __restrict__ dhr_out, bf16* __restrict__ dhc_out,
     float* __restrict__ dcd_out, float* __restrict__ dw3v_out,
     float* __restrict__ gb_out,  // [3*H]: gb1 | gb2 | gb3 column sums
-    float* __restrict__ gw1_out,  // [H][K_OUT] (FUSE_WG only)
+    float* __restrict__ gw1_out,  // FUSE_WG: [H][K_OUT]
+                                  // LIN: tail partials [4*ntile][3*H]
     float* __restrict__ gw2_out,  // [H][H]
     float* __restrict__ gw3_out,  // [H][H]
     long m, int normalize, float eps) {
+  constexpr bool FUSE_WG = MODE == EB_FUSE_WG;
+  constexpr bool LIN = MODE == EB_LIN;
   static_assert(!FUSE_WG || H == 64,
                 "the wgrad-fused variant is tuned for H=64 only");
   constexpr int K_IN = EDB<H>::K_IN;
@@ -316,7 +336,7 @@ void fused_edge_bwd(
     }
     if constexpr (FUSE_WG) __syncthreads();
     // ein -> global (only the split-K wgrad path consumes it)
-    if constexpr (!FUSE_WG) {
+    if constexpr (MODE == EB_PLAIN) {
       for (int idx = lane; idx < 16 * (K_OUT / 8); idx += 64) {
         int e = wave * 16 + idx / (K_OUT / 8);
         if (e >= nedge) continue;
@@ -565,50 +585,99 @@ void fused_edge_bwd(
     // ---- dein = dz1 @ W1 in register passes of <=3 n-tiles ----
     // pass outputs land in in_tile (ein no longer needed). NTK 16-col
     // tiles (9 at H=64) processed 3 per pass to bound live accumulators.
-#pragma unroll
-    for (int pass = 0; pass * 3 < NTK; ++pass) {
+    if constexpr (LIN) {
+      // only the n-tile that holds column 2H, in the k order of the full
+      // product below: dr2 is bit-equal. Nothing goes back into in_tile.
+      constexpr int T2H = 2 * H / 16;
       const bf16* w1tp_ = opaque(w1tp);
-      f32x4 acc[3] = {};
+      f32x4 acc = {};
 #pragma unroll
       for (int kk = 0; kk < H / 32; ++kk) {
         int k = kk * 32 + (lane >> 4) * 8;
         bf16x8 a = lds8(smem, L.z1 + (wave * 16 + (lane & 15)) * H_STRIDE * 2
                                   + k * 2);
+        bf16x8 b = g8(w1tp_ + (T2H * 16 + (lane & 15)) * H + k);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+      }
+      if ((lane & 15) == 0) {
+        float* sc = reinterpret_cast<float*>(smem + L.scal);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          sc[(wave * 16 + (lane >> 4) * 4 + r) * 4 + 2] = acc[r];  // dr2
+      }
+      // dW1 tail: z1 holds dz1 and in_tile still holds ein, whose columns
+      // 2H..2H+2 are the bf16 r2/attr the first layer read (zero on padded
+      // rows, as is dz1), so each product is exact in fp32. Lane c sums
+      // column c over its wave's 16 rows in order; every (tile, wave)
+      // writes its whole partial row.
+      float* tl = gw1_out +
+                  ((e0 >> 6) * 4 + __builtin_amdgcn_readfirstlane(wave)) *
+                      (3 * H);
+#pragma unroll
+      for (int c = lane; c < H; c += 64) {
+        const __bf16* z1 = reinterpret_cast<const __bf16*>(smem + L.z1);
+        const __bf16* ein = reinterpret_cast<const __bf16*>(smem + L.in_tile);
+        float t0 = 0.f, t1 = 0.f, t2 = 0.f;
+        // four rows per trip: a full unroll holds 64 LDS reads in flight
+#pragma unroll 4
+        for (int e = wave * 16; e < wave * 16 + 16; ++e) {
+          float d = (float)z1[e * H_STRIDE + c];
+          t0 += d * (float)ein[e * K_STRIDE + 2 * H];
+          t1 += d * (float)ein[e * K_STRIDE + 2 * H + 1];
+          t2 += d * (float)ein[e * K_STRIDE + 2 * H + 2];
+        }
+        tl[c * 3] = t0;
+        tl[c * 3 + 1] = t1;
+        tl[c * 3 + 2] = t2;
+      }
+    } else {
+#pragma unroll
+      for (int pass = 0; pass * 3 < NTK; ++pass) {
+        const bf16* w1tp_ = opaque(w1tp);
+        f32x4 acc[3] = {};
+#pragma unroll
+        for (int kk = 0; kk < H / 32; ++kk) {
+          int k = kk * 32 + (lane >> 4) * 8;
+          bf16x8 a = lds8(smem, L.z1 + (wave * 16 + (lane & 15)) * H_STRIDE * 2
+                                    + k * 2);
+#pragma unroll
+          for (int nt = 0; nt < 3; ++nt) {
+            if (pass * 3 + nt >= NTK) break;
+            int gc = (pass * 3 + nt) * 16 + (lane & 15);
+            bf16x8 b = g8(w1tp_ + gc * H + k);
+            acc[nt] =
+                __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[nt], 0, 0, 0);
+          }
+        }
+        __bf16* dein = reinterpret_cast<__bf16*>(smem + L.in_tile);
 #pragma unroll
         for (int nt = 0; nt < 3; ++nt) {
           if (pass * 3 + nt >= NTK) break;
-          int gc = (pass * 3 + nt) * 16 + (lane & 15);
-          bf16x8 b = g8(w1tp_ + gc * H + k);
-          acc[nt] =
-              __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[nt], 0, 0, 0);
-        }
-      }
-      __bf16* dein = reinterpret_cast<__bf16*>(smem + L.in_tile);
+          int c = (pass * 3 + nt) * 16 + (lane & 15);
 #pragma unroll
-      for (int nt = 0; nt < 3; ++nt) {
-        if (pass * 3 + nt >= NTK) break;
-        int c = (pass * 3 + nt) * 16 + (lane & 15);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int e = wave * 16 + (lane >> 4) * 4 + r;
-          dein[e * K_STRIDE + c] = (__bf16)acc[nt][r];
-          if (c == 2 * H) {
-            float* sc = reinterpret_cast<float*>(smem + L.scal);
-            sc[e * 4 + 2] = acc[nt][r];  // dr2 (fp32, before bf16 rounding)
+          for (int r = 0; r < 4; ++r) {
+            int e = wave * 16 + (lane >> 4) * 4 + r;
+            dein[e * K_STRIDE + c] = (__bf16)acc[nt][r];
+            if (c == 2 * H) {
+              float* sc = reinterpret_cast<float*>(smem + L.scal);
+              sc[e * 4 + 2] = acc[nt][r];  // dr2 (fp32, before bf16 rounding)
+            }
           }
         }
       }
     }
     if constexpr (FUSE_WG) __syncthreads();
     // dh_row / dh_col -> global (coalesced, wave-local rows)
-    for (int idx = lane; idx < 16 * HP; idx += 64) {
-      int e = wave * 16 + idx / HP;
-      if (e >= nedge) continue;
-      int c8 = (idx % HP) * 8;
-      *reinterpret_cast<bf16x8*>(dhr_out + (e0 + e) * H + c8) =
-          lds8(smem, L.in_tile + (e * K_STRIDE + c8) * 2);
-      *reinterpret_cast<bf16x8*>(dhc_out + (e0 + e) * H + c8) =
-          lds8(smem, L.in_tile + (e * K_STRIDE + H + c8) * 2);
+    if constexpr (!LIN) {
+      for (int idx = lane; idx < 16 * HP; idx += 64) {
+        int e = wave * 16 + idx / HP;
+        if (e >= nedge) continue;
+        int c8 = (idx % HP) * 8;
+        *reinterpret_cast<bf16x8*>(dhr_out + (e0 + e) * H + c8) =
+            lds8(smem, L.in_tile + (e * K_STRIDE + c8) * 2);
+        *reinterpret_cast<bf16x8*>(dhc_out + (e0 + e) * H + c8) =
+            lds8(smem, L.in_tile + (e * K_STRIDE + H + c8) * 2);
+      }
     }
     // dcd (wave-local rows)
     if (lane < 16 && wave * 16 + lane < nedge) {
@@ -651,7 +720,7 @@ void fused_edge_bwd(
 
 }  // namespace
 
-template <int H, bool FUSE_WG>
+template <int H, int MODE>
 static std::vector<torch::Tensor> fused_edge_backward_impl(
     torch::Tensor h, torch::Tensor coord, torch::Tensor eattr,
     torch::Tensor row, torch::Tensor col, torch::Tensor dmsg_n,
@@ -659,6 +728,8 @@ static std::vector<torch::Tensor> fused_edge_backward_impl(
     torch::Tensor w2, torch::Tensor b2, torch::Tensor w3, torch::Tensor b3,
     torch::Tensor w3v, bool normalize, double eps,
     std::vector<torch::Tensor> prepped) {
+  constexpr bool FUSE_WG = MODE == EB_FUSE_WG;
+  constexpr bool LIN = MODE == EB_LIN;
   long m = row.numel();
   constexpr int K_IN = EDB<H>::K_IN;
   constexpr int K_PAD = EDB<H>::K_PAD;
@@ -666,21 +737,35 @@ static std::vector<torch::Tensor> fused_edge_backward_impl(
   auto bopt = h.options();
   auto fopt = coord.options().dtype(torch::kFloat);
   long edge_rows = FUSE_WG ? 0 : m;  // per-edge buffers only when needed
-  auto ein = torch::empty({edge_rows, (long)K_OUT}, bopt);
+  auto ein = torch::empty({LIN ? 0 : edge_rows, (long)K_OUT}, bopt);
   auto t1 = torch::empty({edge_rows, (long)H}, bopt);
   auto msg = torch::empty({edge_rows, (long)H}, bopt);
   auto dz1 = torch::empty({edge_rows, (long)H}, bopt);
   auto dz2 = torch::empty({edge_rows, (long)H}, bopt);
   auto dz3 = torch::empty({edge_rows, (long)H}, bopt);
-  auto dhr = torch::empty({m, (long)H}, bopt);
-  auto dhc = torch::empty({m, (long)H}, bopt);
+  auto dhr = torch::empty({LIN ? 0 : m, (long)H}, bopt);
+  auto dhc = torch::empty({LIN ? 0 : m, (long)H}, bopt);
   auto dcd = torch::empty({m, 3}, fopt);
-  auto dw3v = torch::zeros({(long)H}, fopt);
-  auto gb = torch::zeros({3 * (long)H}, fopt);
+  torch::Tensor dw3v, gb, tail_part;
+  if (LIN) {
+    // one fill for the two atomically accumulated outputs
+    auto acc = torch::zeros({4 * (long)H}, fopt);
+    dw3v = acc.narrow(0, 0, H);
+    gb = acc.narrow(0, H, 3 * H);
+    // one partial row of the dW1 tail per (tile, wave); the kernel writes
+    // every row
+    tail_part = torch::empty({4 * ((m + TILE - 1) / TILE), 3 * (long)H}, fopt);
+  } else {
+    dw3v = torch::zeros({(long)H}, fopt);
+    gb = torch::zeros({3 * (long)H}, fopt);
+  }
   auto gw1 = torch::zeros({FUSE_WG ? (long)H : 0, (long)K_OUT}, fopt);
   auto gw2 = torch::zeros({FUSE_WG ? (long)H : 0, (long)H}, fopt);
   auto gw3 = torch::zeros({FUSE_WG ? (long)H : 0, (long)H}, fopt);
   if (m == 0) {
+    if (LIN)
+      return {t1, msg, dz1, dz2, dz3, dcd, dw3v, gb,
+              torch::zeros({(long)H, 3}, fopt)};
     if (FUSE_WG) return {dhr, dhc, dcd, dw3v, gb, gw1, gw2, gw3};
     return {ein, t1, msg, dz1, dz2, dz3, dhr, dhc, dcd, dw3v, gb};
   }
@@ -722,7 +807,7 @@ static std::vector<torch::Tensor> fused_edge_backward_impl(
     b3c = b3.contiguous().to(torch::kFloat);
     w3vc = w3v.contiguous().to(torch::kFloat);
   }
-  fused_edge_bwd<H, FUSE_WG><<<blocks, THREADS, L.total, stream>>>(
+  fused_edge_bwd<H, MODE><<<blocks, THREADS, L.total, stream>>>(
       reinterpret_cast<const bf16*>(hc.data_ptr()), cc.data_ptr<float>(),
       ec.data_ptr<float>(), row.contiguous().data_ptr<long>(),
       col.contiguous().data_ptr<long>(),
@@ -743,10 +828,16 @@ static std::vector<torch::Tensor> fused_edge_backward_impl(
       reinterpret_cast<bf16*>(dhr.data_ptr()),
       reinterpret_cast<bf16*>(dhc.data_ptr()), dcd.data_ptr<float>(),
       dw3v.data_ptr<float>(), gb.data_ptr<float>(),
-      FUSE_WG ? gw1.data_ptr<float>() : nullptr,
+      FUSE_WG ? gw1.data_ptr<float>()
+              : (LIN ? tail_part.data_ptr<float>() : nullptr),
       FUSE_WG ? gw2.data_ptr<float>() : nullptr,
       FUSE_WG ? gw3.data_ptr<float>() : nullptr, m, normalize ? 1 : 0,
       (float)eps);
+  if (LIN) {
+    // aten's sum is deterministic: a fixed fold over the partial rows
+    auto gw1_tail = tail_part.sum(0).view({(long)H, 3});
+    return {t1, msg, dz1, dz2, dz3, dcd, dw3v, gb, gw1_tail};
+  }
   if (FUSE_WG) return {dhr, dhc, dcd, dw3v, gb, gw1, gw2, gw3};
   return {ein, t1, msg, dz1, dz2, dz3, dhr, dhc, dcd, dw3v, gb};
 }
@@ -762,14 +853,14 @@ std::vector<torch::Tensor> fused_edge_backward(
   TORCH_CHECK(hdim == 32 || hdim == 64 || hdim == 128,
               "fused edge backward supports hidden_nf in {32, 64, 128}");
   if (hdim == 32)
-    return fused_edge_backward_impl<32, false>(
+    return fused_edge_backward_impl<32, EB_PLAIN>(
         h, coord, eattr, row, col, dmsg_n, dtrans_n, w1, b1, w2, b2, w3,
         b3, w3v, normalize, eps, std::move(prepped));
   if (hdim == 128)
-    return fused_edge_backward_impl<128, false>(
+    return fused_edge_backward_impl<128, EB_PLAIN>(
         h, coord, eattr, row, col, dmsg_n, dtrans_n, w1, b1, w2, b2, w3,
         b3, w3v, normalize, eps, std::move(prepped));
-  return fused_edge_backward_impl<64, false>(
+  return fused_edge_backward_impl<64, EB_PLAIN>(
       h, coord, eattr, row, col, dmsg_n, dtrans_n, w1, b1, w2, b2, w3, b3,
       w3v, normalize, eps, std::move(prepped));
 }
@@ -786,7 +877,33 @@ std::vector<torch::Tensor> fused_edge_backward_wg(
     std::vector<torch::Tensor> prepped) {
   TORCH_CHECK(h.size(1) == 64,
               "the wgrad-fused edge backward is tuned for hidden_nf=64");
-  return fused_edge_backward_impl<64, true>(
+  return fused_edge_backward_impl<64, EB_FUSE_WG>(
+      h, coord, eattr, row, col, dmsg_n, dtrans_n, w1, b1, w2, b2, w3, b3,
+      w3v, normalize, eps, std::move(prepped));
+}
+
+// node-sum variant (EB_LIN): returns {t1, msg, dz1, dz2, dz3, dcd, dw3v, gb,
+// gw1_tail [H,3] f32}. No ein, dh_row or dh_col: the caller takes dh and
+// the h-columns of dW1 from the per-node sums of dz1.
+std::vector<torch::Tensor> fused_edge_backward_lin(
+    torch::Tensor h, torch::Tensor coord, torch::Tensor eattr,
+    torch::Tensor row, torch::Tensor col, torch::Tensor dmsg_n,
+    torch::Tensor dtrans_n, torch::Tensor w1, torch::Tensor b1,
+    torch::Tensor w2, torch::Tensor b2, torch::Tensor w3, torch::Tensor b3,
+    torch::Tensor w3v, bool normalize, double eps,
+    std::vector<torch::Tensor> prepped) {
+  long hdim = h.size(1);
+  TORCH_CHECK(hdim == 32 || hdim == 64 || hdim == 128,
+              "fused edge backward supports hidden_nf in {32, 64, 128}");
+  if (hdim == 32)
+    return fused_edge_backward_impl<32, EB_LIN>(
+        h, coord, eattr, row, col, dmsg_n, dtrans_n, w1, b1, w2, b2, w3,
+        b3, w3v, normalize, eps, std::move(prepped));
+  if (hdim == 128)
+    return fused_edge_backward_impl<128, EB_LIN>(
+        h, coord, eattr, row, col, dmsg_n, dtrans_n, w1, b1, w2, b2, w3,
+        b3, w3v, normalize, eps, std::move(prepped));
+  return fused_edge_backward_impl<64, EB_LIN>(
       h, coord, eattr, row, col, dmsg_n, dtrans_n, w1, b1, w2, b2, w3, b3,
       w3v, normalize, eps, std::move(prepped));
 }

@@ -114,12 +114,16 @@ __global__ void seg_reduce_wave_small(const T* __restrict__ data,
 // Each lane loads 4 contiguous elements (b64 for bf16), 4 rows in flight
 // per wave; cross-row combine is a fixed-shape shfl_xor tree (deterministic
 // run-to-run). 4x the bytes/instruction of seg_reduce_wave and 4-way MLP.
-template <typename T>
-__global__ void seg_reduce_wave4(const T* __restrict__ data,
-                                 const long* __restrict__ rowptr,
-                                 const long* __restrict__ perm,
-                                 T* __restrict__ out, long n, int f,
-                                 bool mean) {
+//
+// SPLIT (sum mode): the fp32 sum S leaves as two halves, hi = T(S) at
+// out[seg * ostride + j] and lo = T(S - hi) at lo[seg * lstride + j], so a
+// bf16 consumer can recover S to about 16 mantissa bits. Same reduction
+// order either way: hi is bit-equal to the plain result.
+template <typename T, bool SPLIT>
+__device__ __forceinline__ void seg_wave4_body(
+    const T* __restrict__ data, const long* __restrict__ rowptr,
+    const long* __restrict__ perm, T* __restrict__ out, T* __restrict__ lo,
+    long ostride, long lstride, long n, int f, bool mean) {
   int lane = threadIdx.x & (WAVE - 1);
   int rl = lane >> 4;   // row sublane 0..3
   int fl = lane & 15;   // feature-quad index
@@ -165,14 +169,44 @@ __global__ void seg_reduce_wave4(const T* __restrict__ data,
       a2 += __shfl_xor(a2, 32);
       a3 += __shfl_xor(a3, 32);
       if (rl == 0) {
-        T* o = out + seg * f + fq * 4;
-        o[0] = from_f32<T>(a0 * inv);
-        o[1] = from_f32<T>(a1 * inv);
-        o[2] = from_f32<T>(a2 * inv);
-        o[3] = from_f32<T>(a3 * inv);
+        T* o = out + seg * (SPLIT ? ostride : (long)f) + fq * 4;
+        T h0 = from_f32<T>(a0 * inv), h1 = from_f32<T>(a1 * inv);
+        T h2 = from_f32<T>(a2 * inv), h3 = from_f32<T>(a3 * inv);
+        o[0] = h0;
+        o[1] = h1;
+        o[2] = h2;
+        o[3] = h3;
+        if constexpr (SPLIT) {
+          T* l = lo + seg * lstride + fq * 4;
+          l[0] = from_f32<T>(a0 * inv - to_f32<T>(h0));
+          l[1] = from_f32<T>(a1 * inv - to_f32<T>(h1));
+          l[2] = from_f32<T>(a2 * inv - to_f32<T>(h2));
+          l[3] = from_f32<T>(a3 * inv - to_f32<T>(h3));
+        }
       }
     }
   }
+}
+
+template <typename T>
+__global__ void seg_reduce_wave4(const T* __restrict__ data,
+                                 const long* __restrict__ rowptr,
+                                 const long* __restrict__ perm,
+                                 T* __restrict__ out, long n, int f,
+                                 bool mean) {
+  seg_wave4_body<T, false>(data, rowptr, perm, out, nullptr, f, f, n, f,
+                           mean);
+}
+
+template <typename T>
+__global__ void seg_reduce_wave4_split(const T* __restrict__ data,
+                                       const long* __restrict__ rowptr,
+                                       const long* __restrict__ perm,
+                                       T* __restrict__ hi, T* __restrict__ lo,
+                                       long hstride, long lstride, long n,
+                                       int f) {
+  seg_wave4_body<T, true>(data, rowptr, perm, hi, lo, hstride, lstride, n, f,
+                          false);
 }
 
 // ---------------------------------------------------------------------------
@@ -675,6 +709,57 @@ torch::Tensor segment_reduce_csr_perm(torch::Tensor data,
 torch::Tensor segment_reduce_csr(torch::Tensor data, torch::Tensor rowptr,
                                  bool mean) {
   return segment_reduce_csr_perm(data, rowptr, torch::Tensor(), mean);
+}
+
+// Sum of bf16 rows per CSR segment as (hi, lo) bf16 halves of the fp32
+// accumulator (seg_reduce_wave4, sum mode, f in {32, 64, 128}). hi_out and
+// lo_out, when given, are [n, f] bf16 views with unit column stride, for
+// instance column slices of an [n, 2f] buffer that a GEMM reads whole.
+std::vector<torch::Tensor> segment_reduce_csr_split(
+    torch::Tensor data, torch::Tensor rowptr,
+    c10::optional<torch::Tensor> perm, c10::optional<torch::Tensor> hi_out,
+    c10::optional<torch::Tensor> lo_out) {
+  TORCH_CHECK(data.is_cuda() && rowptr.is_cuda(), "expected CUDA tensors");
+  TORCH_CHECK(data.scalar_type() == torch::kBFloat16 && data.dim() == 2,
+              "segment_reduce_csr_split: data must be [M, f] bf16");
+  TORCH_CHECK(rowptr.scalar_type() == torch::kLong, "rowptr must be int64");
+  const long f = data.size(1);
+  TORCH_CHECK(f == 32 || f == 64 || f == 128,
+              "segment_reduce_csr_split: f must be 32, 64 or 128");
+  auto d = data.contiguous();
+  auto rp = rowptr.contiguous();
+  const long* pp = nullptr;
+  torch::Tensor pc;
+  if (perm.has_value() && perm->defined() && perm->numel() > 0) {
+    TORCH_CHECK(perm->is_cuda() && perm->scalar_type() == torch::kLong,
+                "perm must be CUDA int64");
+    pc = perm->contiguous();
+    pp = pc.data_ptr<long>();
+  }
+  const long n = rp.numel() - 1;
+  auto pick = [&](c10::optional<torch::Tensor>& o, const char* name) {
+    if (!o.has_value() || !o->defined()) return torch::empty({n, f}, d.options());
+    TORCH_CHECK(o->is_cuda() && o->scalar_type() == torch::kBFloat16 &&
+                    o->dim() == 2 && o->size(0) == n && o->size(1) == f &&
+                    (n <= 1 || o->stride(0) >= f) && o->stride(1) == 1 &&
+                    o->stride(0) % 4 == 0 &&
+                    reinterpret_cast<uintptr_t>(o->data_ptr()) % 8 == 0,
+                "segment_reduce_csr_split: ", name,
+                " must be an [n, f] bf16 view with unit column stride");
+    return *o;
+  };
+  auto hi = pick(hi_out, "hi_out");
+  auto lo = pick(lo_out, "lo_out");
+  if (n == 0) return {hi, lo};
+  auto stream = at::hip::getCurrentHIPStream();
+  using T = __hip_bfloat16;
+  const int threads = 256;
+  seg_reduce_wave4_split<T><<<num_blocks(n * WAVE, threads), threads, 0,
+                              stream>>>(
+      reinterpret_cast<const T*>(d.data_ptr()), rp.data_ptr<long>(), pp,
+      reinterpret_cast<T*>(hi.data_ptr()), reinterpret_cast<T*>(lo.data_ptr()),
+      hi.stride(0), lo.stride(0), n, (int)f);
+  return {hi, lo};
 }
 
 namespace {

@@ -128,6 +128,47 @@ def edge_backward(fwd, row, col, dmsg_n, dtrans_n, w1, w2, w3, w3v,
                 gw3=dz3.t() @ fwd["msg"], gh=gh, gc=gc)
 
 
+def edge_backward_factored(fwd, h, eattr, row, col, dmsg_n, dtrans_n, w1, w2,
+                           w3, w3v, num_nodes):
+    """``edge_backward`` with dh and dW1 taken from per-NODE sums of dz1.
+
+    z1 is linear in ein and ein = [h_i | h_j | r2 | a] gathers node rows, so
+    with S_row[n] = sum of dz1 over the edges whose row is n and S_col
+    likewise over col (both [N,H]):
+
+      gh            = S_row W1[:, :H] + S_col W1[:, H:2H]
+      gw1[:, :H]    = S_row^T h        gw1[:, H:2H] = S_col^T h
+      gw1[:, 2H:]   = sum_e dz1_e (x) [r2_e, a_e]     (per edge, three columns)
+      dr2_e         = dz1_e . W1[:, 2H]               (all of dein that dcd needs)
+
+    No [M, 2H+3] dein or ein product is formed. Returns the dict of
+    ``edge_backward`` without dein/dhr/dhc, plus s_row, s_col, gw1_tail."""
+    hdim = w1.size(0)
+    dtrans_e = dtrans_n.index_select(0, row)
+    dp = head_cotangent(dtrans_e, fwd["d"], fwd["inv"])
+    dz3 = dz_head(dp, w3v, fwd["z3"])
+    dz2 = dz_hidden(dmsg_n.index_select(0, row) + dz3 @ w3, fwd["z2"])
+    dz1 = dz_hidden(dz2 @ w2, fwd["z1"])
+    s_row = torch.zeros(num_nodes, hdim, dtype=dz1.dtype, device=dz1.device)
+    s_row.index_add_(0, row, dz1)
+    s_col = torch.zeros_like(s_row).index_add_(0, col, dz1)
+    gh = s_row @ w1[:, :hdim] + s_col @ w1[:, hdim:2 * hdim]
+    tail_in = torch.cat([fwd["r2"].unsqueeze(1).to(dz1.dtype),
+                         eattr.to(dz1.dtype)], dim=1)
+    gw1_tail = dz1.t() @ tail_in
+    gw1 = torch.cat([s_row.t() @ h, s_col.t() @ h, gw1_tail], dim=1)
+    dr2 = dz1 @ w1[:, 2 * hdim]
+    dcd = dcoord_diff(fwd["p"], dtrans_e, fwd["inv"], fwd["d"], dr2)
+    gc = torch.zeros(num_nodes, 3, dtype=dcd.dtype, device=dcd.device)
+    gc.index_add_(0, row, dcd).index_add_(0, col, -dcd)
+    return dict(dp=dp, dz3=dz3, dz2=dz2, dz1=dz1, dr2=dr2, dcd=dcd,
+                s_row=s_row, s_col=s_col, gw1_tail=gw1_tail,
+                dw3v=dw3v(dp, fwd["z3"]),
+                gb=torch.cat([dz1.sum(0), dz2.sum(0), dz3.sum(0)]),
+                gw1=gw1, gw2=dz2.t() @ fwd["t1"],
+                gw3=dz3.t() @ fwd["msg"], gh=gh, gc=gc)
+
+
 def edge_block_mean(h, coord, eattr, row, col, w1, b1, w2, b2, w3, b3, w3v,
                     normalize, eps):
     """(agg_msg [N,H], agg_trans [N,3]): per-node means over the row

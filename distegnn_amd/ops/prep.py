@@ -66,9 +66,18 @@ def pad_gpad(t: torch.Tensor) -> torch.Tensor:
     return F.pad(t.detach().bfloat16(), (0, 64 - t.size(1))).contiguous()
 
 
+def hh_t(t: torch.Tensor) -> torch.Tensor:
+    """Edge W1 [H, 2H+k] -> [H, 2H] bf16 holding [W1[:, :H]^T | W1[:, H:2H]^T]:
+    the B matrix of ``gh = [S_row | S_col] @ B^T`` in the edge backward."""
+    h = t.size(0)
+    w = t.detach().bfloat16()
+    return torch.cat([w[:, :h].t(), w[:, h:2 * h].t()], dim=1).contiguous()
+
+
 _TRANSFORMS: Dict[str, Callable[[torch.Tensor], torch.Tensor]] = {
     "bf16": bf16c, "f32": f32c, "pad_kpad": pad_kpad,
     "tpad_kout": tpad_kout, "t_bf16": t_bf16, "pad_gpad": pad_gpad,
+    "hh_t": hh_t,
 }
 
 # (id(tensor), kind) -> [version, buffer, source-tensor-ref]
