@@ -652,20 +652,35 @@ def _warn_fallback(op: str, reason: str):
           f"({reason}); running the eager composition instead — expect a "
           f"large per-step slowdown. The hand-written gfx950 kernels cover "
           f"hidden_nf in {{32, 64, 128}} (edge and virtual blocks), "
-          f"edge_attr_nf=2, virtual_channels<=8, bf16. "
-          f"(fp32 evaluation is the reference-parity default and is "
-          f"expected to take this path; set train.bf16_eval=true to "
-          f"evaluate on the fused bf16 kernels.)",
+          f"edge_attr_nf=2, virtual_channels<=8, in bf16 (forward and "
+          f"backward) and in fp32 when no gradient is needed (forward "
+          f"only: fp32 evaluation under no_grad runs fused, fp32 training "
+          f"takes this path).",
           flush=True)
 
 
-def _edge_fallback_reason(h, eattr, rowptr, colptr, col_perm):
+def _dtype_fallback_reason(dtype):
+    if dtype == torch.float32:
+        return ("dtype torch.float32 with a gradient needed (the fp32 "
+                "kernels are forward-only)")
+    return f"dtype {dtype} (kernels are bf16 or forward-only fp32)"
+
+
+def _no_grad_needed(*tensors):
+    return not (torch.is_grad_enabled()
+                and any(t.requires_grad for t in tensors))
+
+
+def _edge_fallback_reason(h, eattr, rowptr, colptr, col_perm,
+                          dtype_ok=None):
     if not h.is_cuda or hip_ext() is None:
         return None            # CPU / no extension: expected, don't warn
     if os.environ.get("DISTEGNN_DISABLE_FUSED") == "1":
         return None            # explicit opt-out
-    if h.dtype != torch.bfloat16:
-        return f"dtype {h.dtype} (kernels are bf16-in/fp32-accum)"
+    if dtype_ok is None:
+        dtype_ok = h.dtype == torch.bfloat16
+    if not dtype_ok:
+        return _dtype_fallback_reason(h.dtype)
     if h.size(1) not in (32, 64, 128):
         return (f"hidden_nf={h.size(1)} (the edge kernels are compiled "
                 f"for H in {{32, 64, 128}})")
@@ -677,23 +692,57 @@ def _edge_fallback_reason(h, eattr, rowptr, colptr, col_perm):
     return None
 
 
+def _edge_block_f32(h, coord, eattr, row, col, rowptr, params, normalize,
+                    eps):
+    """Forward-only fp32 edge block: csrc/fused_edge_f32.hip, then the CSR
+    segment means (which dispatch fp32). No autograd node: the caller has
+    established that no gradient is needed."""
+    ext = _require_ext("fused_edge_block")
+    from . import prep
+
+    w1, b1, w2, b2, w3, b3, w3v = params
+    with torch.no_grad():
+        prepped = [prep.get(t, "frag16_f32") for t in (w1, w2, w3)] + [
+            prep.get(t, "f32") for t in (b1, b2, b3, w3v)]
+        msg, trans = ext.fused_edge_forward_f32(
+            h, coord, eattr, row, col, w1, b1, w2, b2, w3, b3, w3v,
+            bool(normalize), float(eps), prepped)
+        return (ext.segment_reduce_csr(msg, rowptr, True),
+                ext.segment_reduce_csr(trans, rowptr, True))
+
+
 def fused_edge_block(h, coord, eattr, row, col, rowptr, colptr, col_perm,
                      w1, b1, w2, b2, w3, b3, w3v, normalize, eps):
-    """Dispatch: HIP fused kernel on GPU bf16 H=64, eager otherwise.
+    """Dispatch: HIP fused kernels on GPU with hidden_nf in {32, 64, 128}
+    and edge_attr_nf=2 — bf16 (forward and backward), or all-fp32 when no
+    gradient is needed (forward only, csrc/fused_edge_f32.hip); the eager
+    composition otherwise.
 
-    Returns (agg_msg [N,64], agg_trans [N,3]) — per-node MEANS of the edge
+    Returns (agg_msg [N,H], agg_trans [N,3]) — per-node MEANS of the edge
     messages and coordinate translations."""
-    usable = (h.is_cuda and h.dtype == torch.bfloat16
-              and h.size(1) in (32, 64, 128)
-              and eattr is not None and eattr.size(1) == 2
-              and rowptr is not None and colptr is not None
-              and col_perm is not None and hip_ext() is not None
-              and os.environ.get("DISTEGNN_DISABLE_FUSED") != "1")
-    if usable:
+    shape_ok = (h.is_cuda and h.size(1) in (32, 64, 128)
+                and eattr is not None and eattr.size(1) == 2
+                and rowptr is not None and colptr is not None
+                and col_perm is not None and hip_ext() is not None
+                and os.environ.get("DISTEGNN_DISABLE_FUSED") != "1")
+    if shape_ok and h.dtype == torch.bfloat16:
         return _FusedEdgeBlockFn.apply(
             h, coord, eattr, row, col, rowptr, colptr, col_perm,
             w1, b1, w2, b2, w3, b3, w3v, normalize, eps)
-    reason = _edge_fallback_reason(h, eattr, rowptr, colptr, col_perm)
+    params = (w1, b1, w2, b2, w3, b3, w3v)
+    f32_fwd = (h.is_cuda
+               and all(t.dtype == torch.float32
+                       for t in (h, coord, eattr) + params
+                       if t is not None)
+               and hasattr(hip_ext(), "fused_edge_forward_f32")
+               and _no_grad_needed(h, coord, *params))
+    if shape_ok and f32_fwd:
+        return _edge_block_f32(h, coord, eattr, row, col, rowptr, params,
+                               normalize, eps)
+    reason = _edge_fallback_reason(h, eattr, rowptr, colptr, col_perm,
+                                   dtype_ok=bool(
+                                       f32_fwd
+                                       or h.dtype == torch.bfloat16))
     if reason is not None:
         _warn_fallback("fused_edge_block", reason)
     msg, trans = eager_edge_block(
@@ -841,8 +890,9 @@ _VIRTUAL_H = (32, 64, 128)   # instantiations in csrc/fused_virtual.hip
 def fused_virtual_block(h, coord, vcoord, vfeat, gram, batch, ptr, chunks,
                         w1, b1, w2, b2, wxv, bxv, wxvv, wX, bX, wXv):
     """Dispatch: HIP fused kernel on GPU bf16 with hidden_nf in
-    {32, 64, 128} and virtual_channels <= 8, eager otherwise (one warning
-    names the reason; DISTEGNN_DISABLE_FUSED=1 opts out silently).
+    {32, 64, 128} and virtual_channels <= 8, the forward-only fp32 kernel
+    for fp32 inputs when no gradient is needed, eager otherwise (one
+    warning names the reason; DISTEGNN_DISABLE_FUSED=1 opts out silently).
 
     Weight gradients go through ``chunked_wgrad``, whose hand-written
     split-K kernel covers hidden_nf=64 only; at 32 and 128 they take its
@@ -850,15 +900,35 @@ def fused_virtual_block(h, coord, vcoord, vfeat, gram, batch, ptr, chunks,
 
     Returns (v_msg [N,C,H], tv [N,C,3], tx [N,C,3]); the model derives
     trans_v = tv.mean(1), agg_v = v_msg.mean(1), and pools tx / v_msg."""
-    usable = (h.is_cuda and h.dtype == torch.bfloat16
-              and h.size(1) in _VIRTUAL_H
-              and vcoord.size(1) <= 8 and ptr is not None
-              and hip_ext() is not None
-              and os.environ.get("DISTEGNN_DISABLE_FUSED") != "1")
+    shape_ok = (h.is_cuda and h.size(1) in _VIRTUAL_H
+                and vcoord.size(1) <= 8 and ptr is not None
+                and hip_ext() is not None
+                and os.environ.get("DISTEGNN_DISABLE_FUSED") != "1")
+    usable = shape_ok and h.dtype == torch.bfloat16
+    params = (w1, b1, w2, b2, wxv, bxv, wxvv, wX, bX, wXv)
+    # forward-only fp32 kernel (csrc/fused_virtual_f32.hip) when no
+    # gradient is needed
+    f32_fwd = (h.is_cuda
+               and all(t.dtype == torch.float32
+                       for t in (h, coord, vcoord, vfeat, gram) + params)
+               and hasattr(hip_ext(), "fused_virtual_forward_f32")
+               and _no_grad_needed(h, coord, vcoord, vfeat, gram, *params))
+    if shape_ok and not usable and f32_fwd:
+        from . import prep
+
+        with torch.no_grad():
+            prepped = [prep.get(t, "frag16_f32")
+                       for t in (w1, w2, wxv, wX)] + [
+                prep.get(t, "f32") for t in (b1, b2, bxv, bX, wxvv, wXv)]
+            vmsg, tv, tx = hip_ext().fused_virtual_forward_f32(
+                h, coord, vcoord, vfeat, gram, batch, w1, b1, w2, b2, wxv,
+                bxv, wxvv, wX, bX, wXv, prepped)
+        n, c = h.size(0), vcoord.size(1)
+        return vmsg.view(n, c, -1), tv.view(n, c, 3), tx.view(n, c, 3)
     if (not usable and h.is_cuda and hip_ext() is not None
             and os.environ.get("DISTEGNN_DISABLE_FUSED") != "1"):
-        if h.dtype != torch.bfloat16:
-            reason = f"dtype {h.dtype} (kernels are bf16-in/fp32-accum)"
+        if h.dtype != torch.bfloat16 and not f32_fwd:
+            reason = _dtype_fallback_reason(h.dtype)
         elif h.size(1) not in _VIRTUAL_H:
             reason = (f"hidden_nf={h.size(1)} (the virtual-block kernels are "
                       f"compiled for H in {{32, 64, 128}})")

@@ -23,9 +23,11 @@ SOURCES = [
     os.path.join(_CSRC, "radius.hip"),
     os.path.join(_CSRC, "fused_edge.hip"),
     os.path.join(_CSRC, "fused_edge_bwd.hip"),
+    os.path.join(_CSRC, "fused_edge_f32.hip"),
     os.path.join(_CSRC, "wgrad.hip"),
     os.path.join(_CSRC, "tall_linear.hip"),
     os.path.join(_CSRC, "fused_virtual.hip"),
+    os.path.join(_CSRC, "fused_virtual_f32.hip"),
     os.path.join(_CSRC, "elementwise.hip"),
     os.path.join(_CSRC, "cfconv.hip"),
 ]

@@ -91,6 +91,21 @@ std::vector<torch::Tensor> segment_reduce_csr_split(
     c10::optional<torch::Tensor> perm, c10::optional<torch::Tensor> hi_out,
     c10::optional<torch::Tensor> lo_out);
 
+std::tuple<torch::Tensor, torch::Tensor> fused_edge_forward_f32(
+    torch::Tensor h, torch::Tensor coord, torch::Tensor eattr,
+    torch::Tensor row, torch::Tensor col, torch::Tensor w1, torch::Tensor b1,
+    torch::Tensor w2, torch::Tensor b2, torch::Tensor w3, torch::Tensor b3,
+    torch::Tensor w3v, bool normalize, double eps,
+    std::vector<torch::Tensor> prepped = {});
+torch::Tensor mfma_probe_f32(torch::Tensor a, torch::Tensor bt);
+std::vector<torch::Tensor> fused_virtual_forward_f32(
+    torch::Tensor h, torch::Tensor coord, torch::Tensor vcoord,
+    torch::Tensor vfeat, torch::Tensor gram, torch::Tensor batch,
+    torch::Tensor w1, torch::Tensor b1, torch::Tensor w2, torch::Tensor b2,
+    torch::Tensor wxv, torch::Tensor bxv, torch::Tensor wxvv,
+    torch::Tensor wX, torch::Tensor bX, torch::Tensor wXv,
+    std::vector<torch::Tensor> prepped = {});
+
 torch::Tensor radius_graph(torch::Tensor pos, double r) {
   return std::get<0>(radius_graph_gpu(pos, r));
 }
@@ -212,4 +227,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_probe", &mfma_probe,
         "16x16x32 bf16 MFMA layout probe: D = A @ B (bt = B^T)",
         py::arg("a"), py::arg("bt"));
+  m.def("mfma_probe_f32", &mfma_probe_f32,
+        "16x16x4 f32 MFMA layout probe: D = A @ B (a [16,4], bt = B^T [16,4])",
+        py::arg("a"), py::arg("bt"));
+  m.def("fused_edge_forward_f32", &fused_edge_forward_f32,
+        "forward-only fp32 fused edge block (f32 MFMA): {msg [M,H], "
+        "trans [M,3]}, both fp32, bitwise reproducible",
+        py::arg("h"), py::arg("coord"), py::arg("eattr"), py::arg("row"),
+        py::arg("col"), py::arg("w1"), py::arg("b1"), py::arg("w2"),
+        py::arg("b2"), py::arg("w3"), py::arg("b3"), py::arg("w3v"),
+        py::arg("normalize"), py::arg("eps"),
+        py::arg("prepped") = std::vector<torch::Tensor>{});
+  m.def("fused_virtual_forward_f32", &fused_virtual_forward_f32,
+        "forward-only fp32 fused virtual-edge block (f32 MFMA): {vmsg "
+        "[N*C,H], tv [N*C,3], tx [N*C,3]}, all fp32, bitwise reproducible",
+        py::arg("h"), py::arg("coord"), py::arg("vcoord"), py::arg("vfeat"),
+        py::arg("gram"), py::arg("batch"), py::arg("w1"), py::arg("b1"),
+        py::arg("w2"), py::arg("b2"), py::arg("wxv"), py::arg("bxv"),
+        py::arg("wxvv"), py::arg("wX"), py::arg("bX"), py::arg("wXv"),
+        py::arg("prepped") = std::vector<torch::Tensor>{});
 }

@@ -50,6 +50,20 @@ def pad_kpad(t: torch.Tensor) -> torch.Tensor:
     return F.pad(t.detach().bfloat16(), (0, k_pad - t.size(1))).contiguous()
 
 
+def frag16_f32(t: torch.Tensor) -> torch.Tensor:
+    """[H, k] -> fp32 [roundup16(k)/16, H/16, 64, 4]: a weight of the fp32
+    forward kernels in the order their MFMA loop reads it (csrc/mfma_f32.h).
+    Columns are zero padded to a multiple of the 16-wide k-step; entry
+    [kk, nt, lane] is the float4 W[nt*16 + (lane & 15)][kk*16 + (lane >> 4)*4
+    .. +3], so one wave load is 1 KiB contiguous. Both blocks' W1 land on
+    2H+16 columns (edge k = 2H+3, virtual k = 2H+1+C <= 2H+9)."""
+    h, k = t.shape
+    k_pad = (k + 15) // 16 * 16
+    w = F.pad(t.detach().float(), (0, k_pad - k))
+    return (w.view(h // 16, 16, k_pad // 16, 4, 4).permute(2, 0, 3, 1, 4)
+            .reshape(k_pad // 16, h // 16, 64, 4).contiguous())
+
+
 def tpad_kout(t: torch.Tensor) -> torch.Tensor:
     """[O, k] -> [roundup16(k), O] bf16 (transpose, row zero-pad)."""
     tt = t.detach().bfloat16().t().contiguous()
@@ -77,8 +91,14 @@ def hh_t(t: torch.Tensor) -> torch.Tensor:
 _TRANSFORMS: Dict[str, Callable[[torch.Tensor], torch.Tensor]] = {
     "bf16": bf16c, "f32": f32c, "pad_kpad": pad_kpad,
     "tpad_kout": tpad_kout, "t_bf16": t_bf16, "pad_gpad": pad_gpad,
-    "hh_t": hh_t,
+    "hh_t": hh_t, "frag16_f32": frag16_f32,
 }
+
+# Kinds read only by eager no-grad code (the fp32 evaluation kernels), never
+# by a captured graph: ``get`` brings them up to date at their next use, so
+# ``refresh`` / ``any_stale`` leave them alone and a training step pays
+# nothing for the copies an evaluation epoch left behind.
+_LAZY_KINDS = frozenset({"frag16_f32"})
 
 # (id(tensor), kind) -> [version, buffer, source-tensor-ref]
 _CACHE: Dict[Tuple[int, str], list] = {}
@@ -111,7 +131,7 @@ def refresh() -> int:
     n = 0
     for (tid, kind), ent in _CACHE.items():
         t = ent[2]
-        if ent[0] != t._version:
+        if kind not in _LAZY_KINDS and ent[0] != t._version:
             ent[1].copy_(_TRANSFORMS[kind](t))
             ent[0] = t._version
             n += 1
@@ -121,7 +141,9 @@ def refresh() -> int:
 def any_stale() -> bool:
     """Host-only version scan (no kernels) — lets GraphedStep decide
     whether a side-stream refresh is needed before replaying."""
-    return any(ent[0] != ent[2]._version for ent in _CACHE.values())
+    return any(ent[0] != ent[2]._version
+               for (_, kind), ent in _CACHE.items()
+               if kind not in _LAZY_KINDS)
 
 
 def clear():
