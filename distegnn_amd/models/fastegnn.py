@@ -249,15 +249,30 @@ class EGCLVel(nn.Module):
                 agg = ops.segment_sum(trans, row, n, rowptr=rowptr)
             else:
                 raise ValueError(f"coords_agg {self.coords_agg}")
+        # --- node block, phi_h + phi_v ----------------------------------
+        # One kernel pair for both per-node MLPs (ops.fused_node_block;
+        # csrc/fused_node.hip): h, agg_e, agg_v and node_attr all exist
+        # here. A layer whose feature update is skipped needs phi_v only.
+        skip = self.skip_feature_update
+        if skip:
+            h_out, phiv = ops.fused_node_block(
+                h, None, None, None, self.node_mlp, self.coord_mlp_vel,
+                self.residual, vel_only=True)
+        else:
+            if not fuse:
+                agg_e = ops.segment_mean(edge_feat, row, n, rowptr=rowptr)
+            if not vfuse:
+                agg_v = ops.mid_mean(v_msg)
+            h_out, phiv = ops.fused_node_block(
+                h, agg_e, agg_v, node_attr, self.node_mlp,
+                self.coord_mlp_vel, self.residual)
         # fused tail: coord + agg + trans_v + phi_v(h) * vel in one
         # kernel pair (ops.coord_update; eager composition off-GPU)
-        coord = ops.coord_update(coord, agg, trans_v,
-                                 self.coord_mlp_vel(h), vel)
+        coord = ops.coord_update(coord, agg, trans_v, phiv, vel)
         if self.gravity is not None:
             coord = coord + self.gravity_mlp(h) * self.gravity.to(h.device)
 
         # --- virtual aggregates (fused site B+C collective) -------------
-        skip = self.skip_feature_update
         if not vfuse or skip:
             agg_vc = ops.graph_mean_pool(
                 trans_x.reshape(n, -1), batch, b, ptr=ptr, counts=counts,
@@ -277,23 +292,6 @@ class EGCLVel(nn.Module):
         virtual_coord = virtual_coord + agg_vc
         if skip:
             return h, coord, virtual_feat, virtual_coord
-
-        # --- node model, phi_h ------------------------------------------
-        if not fuse:
-            agg_e = ops.segment_mean(edge_feat, row, n, rowptr=rowptr)
-        if not vfuse:
-            agg_v = ops.mid_mean(v_msg)
-        if node_attr is not None:
-            # in h's dtype: an fp32 node_attr would promote the whole
-            # [N, 3H+A] input to fp32 under autocast, only for the Linear
-            # to cast it straight back
-            node_in = torch.cat([h, agg_e, agg_v, node_attr.to(h.dtype)],
-                                dim=1)
-        else:
-            node_in = torch.cat([h, agg_e, agg_v], dim=1)
-        h_out = self.node_mlp(node_in)
-        if self.residual:
-            h_out = h + h_out
 
         # --- virtual node model, phi_hv ---------------------------------
         vf_out = self.node_mlp_virtual(torch.cat([virtual_feat, agg_vf], dim=-1))

@@ -651,11 +651,13 @@ def _warn_fallback(op: str, reason: str):
     print(f"[distegnn_amd.ops] {op}: fused MFMA kernel not applicable "
           f"({reason}); running the eager composition instead — expect a "
           f"large per-step slowdown. The hand-written gfx950 kernels cover "
-          f"hidden_nf in {{32, 64, 128}} (edge and virtual blocks), "
+          f"hidden_nf in {{32, 64, 128}} (edge and virtual blocks; the "
+          f"node block covers {{32, 64}} with node_attr_nf<=8, a residual "
+          f"SiLU node_mlp of output width hidden_nf, and bf16 only), "
           f"edge_attr_nf=2, virtual_channels<=8, in bf16 (forward and "
           f"backward) and in fp32 when no gradient is needed (forward "
-          f"only: fp32 evaluation under no_grad runs fused, fp32 training "
-          f"takes this path).",
+          f"only: fp32 evaluation under no_grad runs the edge and virtual "
+          f"blocks fused, fp32 training takes this path).",
           flush=True)
 
 
@@ -950,6 +952,185 @@ def fused_virtual_block(h, coord, vcoord, vfeat, gram, batch, ptr, chunks,
             w1, b1, w2, b2, wxv, bxv, wxvv, wX, bX, wXv, train)
     return eager_virtual_block(h, coord, vcoord, vfeat, gram, batch,
                                w1, b1, w2, b2, wxv, bxv, wxvv, wX, bX, wXv)
+
+
+def eager_node_block(h, agg_e, agg_v, attr, node_mlp, vel_mlp, residual,
+                     vel_only):
+    """The composition the fused node block replaces: ``vel_mlp`` on h,
+    ``node_mlp`` on the concatenated input, the residual add.
+
+    Returns (h_out [N,H], phiv [N,1]); h_out is h itself when vel_only."""
+    phiv = vel_mlp(h)
+    if vel_only:
+        return h, phiv
+    if attr is not None:
+        # in h's dtype: an fp32 node_attr would promote the whole
+        # [N, 3H+A] input to fp32 under autocast, only for the Linear
+        # to cast it straight back
+        node_in = torch.cat([h, agg_e, agg_v, attr.to(h.dtype)], dim=1)
+    else:
+        node_in = torch.cat([h, agg_e, agg_v], dim=1)
+    h_out = node_mlp(node_in)
+    if residual:
+        h_out = h + h_out
+    return h_out, phiv
+
+
+class _FusedNodeBlockFn(torch.autograd.Function):
+    """Fused MFMA node block (csrc/fused_node.hip): phi_h with its residual
+    and phi_v in one kernel each way. Only the inputs are saved; the
+    backward kernel recomputes both pre-activations, emits the data
+    gradients and the three operands of the weight gradients, and sums the
+    bias / head / attribute-column gradients itself (per-wave partial rows,
+    folded here by one deterministic sum). The matrix gradients go through
+    the split-K family."""
+
+    @staticmethod
+    def forward(ctx, h, agg_e, agg_v, attr, w1, b1, w2, b2, wv1, bv1, wv2,
+                bv2, vel_only):
+        ext = _require_ext("fused_node_block")
+        from . import prep
+
+        if vel_only:
+            agg_e = agg_v = h
+            w1, b1, w2, b2 = wv1, bv1, wv1, bv1   # never read
+        prepped = [prep.get(w1, "pad_kpad"), prep.get(b1, "bf16"),
+                   prep.get(w2, "bf16"), prep.get(b2, "bf16"),
+                   prep.get(wv1, "bf16"), prep.get(bv1, "bf16"),
+                   prep.get(wv2, "bf16"), prep.get(bv2, "bf16")]
+        h_out, phiv = ext.fused_node_forward(h, agg_e, agg_v, attr, prepped,
+                                             vel_only)
+        ctx.vel_only = vel_only
+        ctx.has_attr = attr is not None
+        ctx.save_for_backward(h, agg_e, agg_v,
+                              attr if attr is not None else h.new_empty(0),
+                              w1, b1, w2, wv1, bv1, wv2, bv2)
+        if vel_only:
+            ctx.mark_non_differentiable(h_out)
+        return h_out, phiv
+
+    @staticmethod
+    def backward(ctx, dh_out, dphiv):
+        (h, agg_e, agg_v, attr, w1, b1, w2, wv1, bv1, wv2,
+         bv2) = ctx.saved_tensors
+        ext = _load_extension()
+        from . import linear as _lin
+        from . import prep
+
+        vel_only = ctx.vel_only
+        n, hd = h.shape
+        if dphiv is None:
+            dphiv = h.new_zeros((n, 1), dtype=torch.float32)
+        if dh_out is None or vel_only:
+            dh_out = h if vel_only else torch.zeros_like(h)
+        prepped = [prep.get(w1, "pad_kpad"), prep.get(w1, "t_bf16"),
+                   prep.get(b1, "bf16"), prep.get(w2, "t_bf16"),
+                   prep.get(wv1, "bf16"), prep.get(wv1, "t_bf16"),
+                   prep.get(bv1, "bf16"), prep.get(wv2, "bf16")]
+        dh_out = dh_out.to(torch.bfloat16).contiguous()
+        dh, dagg_e, dagg_v, dz1, t1, dzv, parts = ext.fused_node_backward(
+            dh_out, dphiv.float().contiguous(), h, agg_e, agg_v,
+            attr if ctx.has_attr else None, prepped, vel_only)
+        sums = parts.sum(0)
+        gbv1 = sums[2 * hd:3 * hd].to(bv1.dtype)
+        gwv2 = sums[3 * hd:4 * hd].view(1, hd).to(wv2.dtype)
+        gbv2 = sums[-1:].to(bv2.dtype)
+        if vel_only:
+            gwv1 = _lin.chunked_wgrad(dzv, h).to(wv1.dtype)
+            return (dh, None, None, None, None, None, None, None, gwv1, gbv1,
+                    gwv2, gbv2, None)
+        g1h, g1e, g1v, gw2 = _lin.grouped_wgrad(
+            [(dz1, h), (dz1, agg_e), (dz1, agg_v), (dh_out, t1)])
+        gwv1 = _lin.chunked_wgrad(dzv, h).to(wv1.dtype)
+        blocks = [g1h, g1e, g1v]
+        if ctx.has_attr:
+            blocks.append(sums[4 * hd:-1].view(hd, -1).to(g1h.dtype))
+        gw1 = torch.cat(blocks, dim=1).to(w1.dtype)
+        return (dh, dagg_e, dagg_v, None, gw1, sums[:hd].to(b1.dtype),
+                gw2.to(w2.dtype), sums[hd:2 * hd].to(w2.dtype), gwv1, gbv1,
+                gwv2, gbv2, None)
+
+
+_NODE_H = (32, 64)   # instantiations in csrc/fused_node.hip
+_NODE_MAX_ATTR = 8
+
+
+def _node_mlps_fusable(node_mlp, vel_mlp, hd, a, vel_only):
+    """Linear-SiLU-Linear twice, with the widths the kernels assume
+    (``vel_only`` never reads node_mlp)."""
+    from torch import nn
+
+    def lsl(m):
+        return (isinstance(m, nn.Sequential) and len(m) == 3
+                and isinstance(m[0], nn.Linear) and isinstance(m[1], nn.SiLU)
+                and isinstance(m[2], nn.Linear)
+                and m[0].bias is not None and m[2].bias is not None)
+
+    node_ok = vel_only or (
+        lsl(node_mlp)
+        and tuple(node_mlp[0].weight.shape) == (hd, 3 * hd + a)
+        and tuple(node_mlp[2].weight.shape) == (hd, hd))
+    return (node_ok and lsl(vel_mlp)
+            and tuple(vel_mlp[0].weight.shape) == (hd, hd)
+            and tuple(vel_mlp[2].weight.shape) == (1, hd))
+
+
+def fused_node_block(h, agg_e, agg_v, attr, node_mlp, vel_mlp, residual=True,
+                     vel_only=False):
+    """phi_h and phi_v of one layer: (h + node_mlp([h|agg_e|agg_v|attr]),
+    vel_mlp(h)) -> (h_out [N,H], phiv [N,1]). ``vel_only`` (a layer whose
+    feature update is skipped) computes phiv alone and returns h unchanged.
+
+    Dispatch: the HIP kernel pair on GPU for bf16 h with hidden_nf in
+    {32, 64}, node_attr_nf <= 8, residual Linear-SiLU-Linear MLPs of output
+    width hidden_nf, any N >= 1; the composition (``eager_node_block``)
+    otherwise, with one warning that names the reason.
+    DISTEGNN_DISABLE_FUSED=1 and DISTEGNN_NODE_EAGER=1 opt out silently.
+    phiv is fp32 from the kernel (``coord_update`` wants fp32), in h's
+    dtype from the composition."""
+    hd = h.size(1)
+    a = 0 if attr is None or vel_only else attr.size(1)
+    opted_out = (os.environ.get("DISTEGNN_DISABLE_FUSED") == "1"
+                 or os.environ.get("DISTEGNN_NODE_EAGER") == "1")
+    reason = None
+    if h.is_cuda and hip_ext() is not None and not opted_out:
+        if not hasattr(hip_ext(), "fused_node_forward"):
+            raise RuntimeError(
+                "distegnn_amd HIP extension lacks fused_node_forward; "
+                "rebuild it (python -m distegnn_amd.ops.build)")
+        if h.dtype != torch.bfloat16:
+            reason = (f"dtype {h.dtype} (the node-block kernels are bf16 "
+                      f"only)")
+        elif hd not in _NODE_H:
+            reason = (f"hidden_nf={hd} (the node-block kernels are compiled "
+                      f"for H in {{32, 64}})")
+        elif a > _NODE_MAX_ATTR:
+            reason = f"node_attr_nf={a} (kernels cover <=8)"
+        elif not residual and not vel_only:
+            reason = "residual=False"
+        elif not _node_mlps_fusable(node_mlp, vel_mlp, hd, a, vel_only):
+            reason = ("node_mlp / coord_mlp_vel are not Linear-SiLU-Linear "
+                      "of width hidden_nf")
+        if reason is None:
+            if h.size(0) == 0:
+                return (h if vel_only else h.new_empty((0, hd)),
+                        h.new_empty((0, 1), dtype=torch.float32))
+            attr_c = (attr.to(h.dtype).contiguous()
+                      if a > 0 else None)
+            h_c = h.contiguous()
+            h_out, phiv = _FusedNodeBlockFn.apply(
+                h_c,
+                None if vel_only else agg_e.to(h.dtype).contiguous(),
+                None if vel_only else agg_v.to(h.dtype).contiguous(),
+                attr_c,
+                node_mlp[0].weight, node_mlp[0].bias,
+                node_mlp[2].weight, node_mlp[2].bias,
+                vel_mlp[0].weight, vel_mlp[0].bias,
+                vel_mlp[2].weight, vel_mlp[2].bias, bool(vel_only))
+            return (h if vel_only else h_out), phiv
+        _warn_fallback("fused_node_block", reason)
+    return eager_node_block(h, agg_e, agg_v, attr, node_mlp, vel_mlp,
+                            residual, vel_only)
 
 
 def radius_graph(pos: torch.Tensor, r: float, loop: bool = False) -> torch.Tensor:

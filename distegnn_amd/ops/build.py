@@ -28,6 +28,7 @@ SOURCES = [
     os.path.join(_CSRC, "tall_linear.hip"),
     os.path.join(_CSRC, "fused_virtual.hip"),
     os.path.join(_CSRC, "fused_virtual_f32.hip"),
+    os.path.join(_CSRC, "fused_node.hip"),
     os.path.join(_CSRC, "elementwise.hip"),
     os.path.join(_CSRC, "cfconv.hip"),
 ]

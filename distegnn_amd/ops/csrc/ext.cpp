@@ -105,6 +105,15 @@ std::vector<torch::Tensor> fused_virtual_forward_f32(
     torch::Tensor wxv, torch::Tensor bxv, torch::Tensor wxvv,
     torch::Tensor wX, torch::Tensor bX, torch::Tensor wXv,
     std::vector<torch::Tensor> prepped = {});
+std::vector<torch::Tensor> fused_node_forward(
+    torch::Tensor h, torch::Tensor agg_e, torch::Tensor agg_v,
+    c10::optional<torch::Tensor> attr, std::vector<torch::Tensor> prepped,
+    bool vel_only);
+std::vector<torch::Tensor> fused_node_backward(
+    torch::Tensor dh_out, torch::Tensor dphiv, torch::Tensor h,
+    torch::Tensor agg_e, torch::Tensor agg_v,
+    c10::optional<torch::Tensor> attr, std::vector<torch::Tensor> prepped,
+    bool vel_only);
 
 torch::Tensor radius_graph(torch::Tensor pos, double r) {
   return std::get<0>(radius_graph_gpu(pos, r));
@@ -246,4 +255,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w2"), py::arg("b2"), py::arg("wxv"), py::arg("bxv"),
         py::arg("wxvv"), py::arg("wX"), py::arg("bX"), py::arg("wXv"),
         py::arg("prepped") = std::vector<torch::Tensor>{});
+  m.def("fused_node_forward", &fused_node_forward,
+        "fused node block forward (bf16 MFMA): phi_h with residual and "
+        "phi_v -> {h_out [N,H] bf16, phiv [N,1] fp32}; vel_only computes "
+        "phiv alone",
+        py::arg("h"), py::arg("agg_e"), py::arg("agg_v"), py::arg("attr"),
+        py::arg("prepped"), py::arg("vel_only"));
+  m.def("fused_node_backward", &fused_node_backward,
+        "fused node block backward: {dh, dagg_e, dagg_v, dz1, t1, dzv "
+        "[N,H] bf16, partial rows of the bias/head/attribute gradients}",
+        py::arg("dh_out"), py::arg("dphiv"), py::arg("h"), py::arg("agg_e"),
+        py::arg("agg_v"), py::arg("attr"), py::arg("prepped"),
+        py::arg("vel_only"));
 }

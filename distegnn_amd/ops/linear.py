@@ -113,18 +113,22 @@ class _SplitKLinearFn(torch.autograd.Function):
     def backward(ctx, g):
         x, w = ctx.saved_tensors
         g = g.contiguous()
-        if ctx.dt == torch.bfloat16 and w.is_cuda and w.dtype != ctx.dt:
-            from . import prep
-
-            wt = prep.get(w, "t_bf16")
+        if not ctx.needs_input_grad[0]:
+            # e.g. the embedding: its input is data, the dgrad is unused
+            gx = None
         else:
-            wt = w.to(g.dtype).t().contiguous()
-        if _ext_ok(g, wt):
-            from . import hip_ext
+            if ctx.dt == torch.bfloat16 and w.is_cuda and w.dtype != ctx.dt:
+                from . import prep
 
-            gx = hip_ext().tall_linear(g, wt, None, 0)
-        else:
-            gx = g @ wt.t()
+                wt = prep.get(w, "t_bf16")
+            else:
+                wt = w.to(g.dtype).t().contiguous()
+            if _ext_ok(g, wt):
+                from . import hip_ext
+
+                gx = hip_ext().tall_linear(g, wt, None, 0)
+            else:
+                gx = g @ wt.t()
         gw = chunked_wgrad(g, x.to(g.dtype)).to(w.dtype)
         gb = g.sum(0).to(w.dtype) if ctx.has_bias else None
         return gx, gw, gb, None
