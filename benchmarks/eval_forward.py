@@ -3,9 +3,13 @@
 Evaluation (runtime/trainer.py ``_eval``) runs the model under
 ``torch.no_grad()`` in fp32 unless ``train.bf16_eval`` is set. This times that
 forward (FastEGNN, L=4, normalisation as in the workload) with the
-forward-only fp32 kernels (csrc/fused_edge_f32.hip, fused_virtual_f32.hip)
-and with ``DISTEGNN_DISABLE_FUSED=1``, the eager composition every fp32
-evaluation took before those kernels existed, on the two headline graphs of
+forward-only fp32 kernels (csrc/fused_edge_f32.hip, fused_virtual_f32.hip,
+fused_node_f32.hip: arm ``fused``), with ``DISTEGNN_NODE_EAGER=1`` (arm
+``node-eager``: the same forward with the node block on its eager
+composition, which is what fp32 evaluation ran before the fp32 node kernel)
+and with ``DISTEGNN_DISABLE_FUSED=1`` (arm ``eager``: the composition every
+fp32 evaluation took before any of those kernels existed), on the two
+headline graphs of
 bench.py: the synthetic LargeFluid-113K graph (C=5) and the Water-3D batch of
 15 graphs (C=3), for each hidden_nf in --widths. Run on a GPU box:
 
@@ -15,8 +19,10 @@ Timing as in hidden_sweep.py: every arm is warmed up first, a timed window
 is --steps forwards between two device events ending in a synchronise, and
 the windows of all arms are interleaved --repeats times in one process. The
 median window and the min..max spread are printed per arm, with the peak
-allocated memory of one forward (above what is resident before it) and the
-relative L2 distance of the two arms' outputs; then one JSON line.
+allocated memory of one forward (above what is resident before it), the
+``eager`` / ``fused`` speed-up, the ``fused`` / ``node-eager`` ratio judged
+against the larger of those two arms' spreads, and the relative L2 distance
+of the fused displacement from each other arm's; then one JSON line.
 """
 
 import argparse
@@ -43,7 +49,14 @@ def load_batch(workload, device):
     return bt.to(device)
 
 
-def make_forward(workload, hidden, batch, device, fused):
+# arm -> the opt-out variable its forwards run under
+ARMS = (("fused", None),
+        ("node-eager", "DISTEGNN_NODE_EAGER"),
+        ("eager", "DISTEGNN_DISABLE_FUSED"))
+_SWITCHES = tuple(v for _, v in ARMS if v is not None)
+
+
+def make_forward(workload, hidden, batch, device, switch):
     import bench
     from distegnn_amd.models import FastEGNN
     from distegnn_amd.runtime.trainer import model_forward
@@ -58,15 +71,16 @@ def make_forward(workload, hidden, batch, device, fused):
     model.eval()
 
     def forward():
-        if fused:
-            os.environ.pop("DISTEGNN_DISABLE_FUSED", None)
-        else:
-            os.environ["DISTEGNN_DISABLE_FUSED"] = "1"
+        for var in _SWITCHES:
+            os.environ.pop(var, None)
+        if switch is not None:
+            os.environ[switch] = "1"
         try:
             with torch.no_grad():
                 return model_forward(model, "FastEGNN", batch, device)
         finally:
-            os.environ.pop("DISTEGNN_DISABLE_FUSED", None)
+            for var in _SWITCHES:
+                os.environ.pop(var, None)
 
     return forward
 
@@ -111,8 +125,8 @@ def main():
               f"{args.steps} forwards/window x {args.repeats}", flush=True)
         arms = {}
         for hdim in widths:
-            for name, fused in (("fused", True), ("eager", False)):
-                fwd = make_forward(workload, hdim, batch, device, fused)
+            for name, switch in ARMS:
+                fwd = make_forward(workload, hdim, batch, device, switch)
                 for _ in range(args.warmup):
                     loc, vloc = fwd()
                 torch.cuda.synchronize()
@@ -125,26 +139,50 @@ def main():
                 times[k].append(window(fwd, args.steps))
         for hdim in widths:
             row = {}
-            for name in ("fused", "eager"):
+            for name, _ in ARMS:
                 fwd = arms[(hdim, name)][0]
                 ts = sorted(times[(hdim, name)])
                 row[name] = (ts[len(ts) // 2], ts[0], ts[-1], peak_mib(fwd))
-            lf, le = arms[(hdim, "fused")][1], arms[(hdim, "eager")][1]
             pos = batch.pos
-            dist = float(((lf - le).double().norm()
-                          / (le - pos).double().norm()))
-            for name in ("fused", "eager"):
+            lf = arms[(hdim, "fused")][1]
+
+            def distance(other):
+                lo_ = arms[(hdim, other)][1]
+                return float(((lf - lo_).double().norm()
+                              / (lo_ - pos).double().norm()))
+
+            dist, dist_ne = distance("eager"), distance("node-eager")
+            for name, _ in ARMS:
                 med, lo, hi, peak = row[name]
-                print(f"{workload:<10s} H={hdim:<4d} {name:<5s} {med:9.2f} "
+                key = name.replace("-", "_")
+                print(f"{workload:<10s} H={hdim:<4d} {name:<10s} {med:9.2f} "
                       f"ms/forward (min {lo:.2f}, max {hi:.2f})  peak "
                       f"{peak:8.0f} MiB")
-                result[f"{workload}_H{hdim}_{name}_ms"] = round(med, 3)
-                result[f"{workload}_H{hdim}_{name}_peak_mib"] = round(peak)
+                result[f"{workload}_H{hdim}_{key}_ms"] = round(med, 3)
+                result[f"{workload}_H{hdim}_{key}_min_ms"] = round(lo, 3)
+                result[f"{workload}_H{hdim}_{key}_max_ms"] = round(hi, 3)
+                result[f"{workload}_H{hdim}_{key}_peak_mib"] = round(peak)
             print(f"{workload:<10s} H={hdim:<4d} speed-up "
                   f"{row['eager'][0] / row['fused'][0]:.2f}x, displacement "
                   f"of the two arms differs by {dist:.2e} (relative L2)")
             result[f"{workload}_H{hdim}_speedup"] = round(
                 row["eager"][0] / row["fused"][0], 3)
+            # fused against the same forward with the node block on the
+            # composition; "within spread": the fused median is not above
+            # the node-eager median by more than the larger min..max spread
+            ratio = row["fused"][0] / row["node-eager"][0]
+            spread = max(row[k][2] - row[k][1] for k in ("fused",
+                                                         "node-eager"))
+            slower = row["fused"][0] - row["node-eager"][0] > spread
+            print(f"{workload:<10s} H={hdim:<4d} fused / node-eager "
+                  f"{ratio:.3f} (larger spread {spread:.2f} ms: fused is "
+                  f"{'SLOWER beyond it' if slower else 'not slower beyond it'}"
+                  f"), displacement of the two arms differs by "
+                  f"{dist_ne:.2e} (relative L2)")
+            result[f"{workload}_H{hdim}_fused_over_node_eager"] = round(
+                ratio, 3)
+            result[f"{workload}_H{hdim}_node_eager_distance"] = dist_ne
+            result[f"{workload}_H{hdim}_fused_not_slower"] = not slower
         del arms, batch
         torch.cuda.empty_cache()
     print(json.dumps(result))

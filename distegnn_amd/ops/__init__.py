@@ -651,13 +651,13 @@ def _warn_fallback(op: str, reason: str):
     print(f"[distegnn_amd.ops] {op}: fused MFMA kernel not applicable "
           f"({reason}); running the eager composition instead — expect a "
           f"large per-step slowdown. The hand-written gfx950 kernels cover "
-          f"hidden_nf in {{32, 64, 128}} (edge and virtual blocks; the "
-          f"node block covers {{32, 64}} with node_attr_nf<=8, a residual "
-          f"SiLU node_mlp of output width hidden_nf, and bf16 only), "
+          f"hidden_nf in {{32, 64, 128}} (the node block: {{32, 64}} in "
+          f"bf16, {{32, 64, 128}} in fp32, with node_attr_nf<=8 and a "
+          f"residual SiLU node_mlp of output width hidden_nf), "
           f"edge_attr_nf=2, virtual_channels<=8, in bf16 (forward and "
           f"backward) and in fp32 when no gradient is needed (forward "
-          f"only: fp32 evaluation under no_grad runs the edge and virtual "
-          f"blocks fused, fp32 training takes this path).",
+          f"only: fp32 evaluation under no_grad runs the edge, virtual and "
+          f"node blocks fused, fp32 training takes this path).",
           flush=True)
 
 
@@ -1052,6 +1052,7 @@ class _FusedNodeBlockFn(torch.autograd.Function):
 
 
 _NODE_H = (32, 64)   # instantiations in csrc/fused_node.hip
+_NODE_H_F32 = (32, 64, 128)   # instantiations in csrc/fused_node_f32.hip
 _NODE_MAX_ATTR = 8
 
 
@@ -1075,19 +1076,52 @@ def _node_mlps_fusable(node_mlp, vel_mlp, hd, a, vel_only):
             and tuple(vel_mlp[2].weight.shape) == (1, hd))
 
 
+def _node_block_f32(h, agg_e, agg_v, attr, node_mlp, vel_mlp, vel_only):
+    """Forward-only fp32 node block: csrc/fused_node_f32.hip. No autograd
+    node: the caller has established that no gradient is needed. The
+    vel-only form hands the kernel h and the coord_mlp_vel weights alone."""
+    ext = _require_ext("fused_node_block")
+    from . import prep
+
+    wv1, bv1 = vel_mlp[0].weight, vel_mlp[0].bias
+    wv2, bv2 = vel_mlp[2].weight, vel_mlp[2].bias
+    with torch.no_grad():
+        vel = [prep.get(wv1, "frag16_f32")] + [
+            prep.get(t, "f32") for t in (bv1, wv2, bv2)]
+        if vel_only:
+            # slots of the node_mlp weights: never read
+            prepped = [vel[0], vel[0], vel[0], vel[1], vel[1]] + vel[1:]
+            _, phiv = ext.fused_node_forward_f32(
+                h.contiguous(), None, None, None, None, None, None, None,
+                wv1, bv1, wv2, bv2, True, prepped)
+            return h, phiv
+        w1, b1 = node_mlp[0].weight, node_mlp[0].bias
+        w2, b2 = node_mlp[2].weight, node_mlp[2].bias
+        prepped = [prep.get(w1, "frag16_f32"), prep.get(w2, "frag16_f32"),
+                   vel[0], prep.get(b1, "f32"), prep.get(b2, "f32")] + vel[1:]
+        h_out, phiv = ext.fused_node_forward_f32(
+            h.contiguous(), agg_e.contiguous(), agg_v.contiguous(),
+            None if attr is None else attr.contiguous(), w1, b1, w2, b2,
+            wv1, bv1, wv2, bv2, False, prepped)
+    return h_out, phiv
+
+
 def fused_node_block(h, agg_e, agg_v, attr, node_mlp, vel_mlp, residual=True,
                      vel_only=False):
     """phi_h and phi_v of one layer: (h + node_mlp([h|agg_e|agg_v|attr]),
     vel_mlp(h)) -> (h_out [N,H], phiv [N,1]). ``vel_only`` (a layer whose
     feature update is skipped) computes phiv alone and returns h unchanged.
 
-    Dispatch: the HIP kernel pair on GPU for bf16 h with hidden_nf in
-    {32, 64}, node_attr_nf <= 8, residual Linear-SiLU-Linear MLPs of output
-    width hidden_nf, any N >= 1; the composition (``eager_node_block``)
-    otherwise, with one warning that names the reason.
-    DISTEGNN_DISABLE_FUSED=1 and DISTEGNN_NODE_EAGER=1 opt out silently.
-    phiv is fp32 from the kernel (``coord_update`` wants fp32), in h's
-    dtype from the composition."""
+    Dispatch, on GPU with node_attr_nf <= 8 and residual Linear-SiLU-Linear
+    MLPs of output width hidden_nf, any N >= 0: the bf16 HIP kernel pair
+    (csrc/fused_node.hip, forward and backward) for bf16 h with hidden_nf in
+    {32, 64}; the forward-only fp32 kernel (csrc/fused_node_f32.hip) with
+    hidden_nf in {32, 64, 128} when h, agg_e, agg_v, attr and every
+    parameter are fp32 and no gradient is needed; the composition
+    (``eager_node_block``) otherwise, with one warning that names the
+    reason. DISTEGNN_DISABLE_FUSED=1 and DISTEGNN_NODE_EAGER=1 opt out
+    silently. phiv is fp32 from the kernels (``coord_update`` wants fp32),
+    in h's dtype from the composition."""
     hd = h.size(1)
     a = 0 if attr is None or vel_only else attr.size(1)
     opted_out = (os.environ.get("DISTEGNN_DISABLE_FUSED") == "1"
@@ -1098,12 +1132,27 @@ def fused_node_block(h, agg_e, agg_v, attr, node_mlp, vel_mlp, residual=True,
             raise RuntimeError(
                 "distegnn_amd HIP extension lacks fused_node_forward; "
                 "rebuild it (python -m distegnn_amd.ops.build)")
-        if h.dtype != torch.bfloat16:
-            reason = (f"dtype {h.dtype} (the node-block kernels are bf16 "
-                      f"only)")
-        elif hd not in _NODE_H:
+        # fp32 tensors the block would read: a candidate for the
+        # forward-only fp32 kernel when no gradient is needed
+        used = [h] if vel_only else [
+            t for t in (h, agg_e, agg_v, attr) if t is not None]
+        used += list(vel_mlp.parameters())
+        if not vel_only:
+            used += list(node_mlp.parameters())
+        all_f32 = all(t.dtype == torch.float32 for t in used)
+        f32_fwd = (all_f32
+                   and hasattr(hip_ext(), "fused_node_forward_f32")
+                   and _no_grad_needed(*used))
+        widths = _NODE_H_F32 if f32_fwd else _NODE_H
+        if h.dtype == torch.float32 and not all_f32:
+            reason = ("dtype torch.float32 with an input or parameter of "
+                      "another dtype (the fp32 node kernel wants all fp32)")
+        elif h.dtype != torch.bfloat16 and not f32_fwd:
+            reason = _dtype_fallback_reason(h.dtype)
+        elif hd not in widths:
             reason = (f"hidden_nf={hd} (the node-block kernels are compiled "
-                      f"for H in {{32, 64}})")
+                      f"for H in {{{', '.join(map(str, widths))}}}"
+                      f"{'' if f32_fwd else ' in bf16'})")
         elif a > _NODE_MAX_ATTR:
             reason = f"node_attr_nf={a} (kernels cover <=8)"
         elif not residual and not vel_only:
@@ -1111,6 +1160,9 @@ def fused_node_block(h, agg_e, agg_v, attr, node_mlp, vel_mlp, residual=True,
         elif not _node_mlps_fusable(node_mlp, vel_mlp, hd, a, vel_only):
             reason = ("node_mlp / coord_mlp_vel are not Linear-SiLU-Linear "
                       "of width hidden_nf")
+        if reason is None and f32_fwd:
+            return _node_block_f32(h, agg_e, agg_v, attr if a > 0 else None,
+                                   node_mlp, vel_mlp, vel_only)
         if reason is None:
             if h.size(0) == 0:
                 return (h if vel_only else h.new_empty((0, hd)),

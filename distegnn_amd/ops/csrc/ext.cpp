@@ -114,6 +114,14 @@ std::vector<torch::Tensor> fused_node_backward(
     torch::Tensor agg_e, torch::Tensor agg_v,
     c10::optional<torch::Tensor> attr, std::vector<torch::Tensor> prepped,
     bool vel_only);
+std::vector<torch::Tensor> fused_node_forward_f32(
+    torch::Tensor h, c10::optional<torch::Tensor> agg_e,
+    c10::optional<torch::Tensor> agg_v, c10::optional<torch::Tensor> attr,
+    c10::optional<torch::Tensor> w1, c10::optional<torch::Tensor> b1,
+    c10::optional<torch::Tensor> w2, c10::optional<torch::Tensor> b2,
+    torch::Tensor wv1, torch::Tensor bv1, torch::Tensor wv2,
+    torch::Tensor bv2, bool vel_only,
+    std::vector<torch::Tensor> prepped = {});
 
 torch::Tensor radius_graph(torch::Tensor pos, double r) {
   return std::get<0>(radius_graph_gpu(pos, r));
@@ -267,4 +275,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dh_out"), py::arg("dphiv"), py::arg("h"), py::arg("agg_e"),
         py::arg("agg_v"), py::arg("attr"), py::arg("prepped"),
         py::arg("vel_only"));
+  m.def("fused_node_forward_f32", &fused_node_forward_f32,
+        "forward-only fp32 fused node block (f32 MFMA): phi_h with residual "
+        "and phi_v -> {h_out [N,H], phiv [N,1]}, both fp32, bitwise "
+        "reproducible; vel_only computes phiv alone (h_out is empty) and "
+        "reads h and the coord_mlp_vel weights only",
+        py::arg("h"), py::arg("agg_e"), py::arg("agg_v"), py::arg("attr"),
+        py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"),
+        py::arg("wv1"), py::arg("bv1"), py::arg("wv2"), py::arg("bv2"),
+        py::arg("vel_only"),
+        py::arg("prepped") = std::vector<torch::Tensor>{});
 }

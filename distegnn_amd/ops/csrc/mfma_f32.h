@@ -21,7 +21,9 @@
 //   [H, 2H)       msg  (written after GEMM2 has read t1)
 // K_STRIDE = K_PAD + 4 and K_PAD = 2H + 16, so K_STRIDE = 20 (mod 32): the
 // 16 rows of a float4 fragment read start 80 bytes apart modulo the 256-byte
-// bank span and cover all 64 banks once.
+// bank span and cover all 64 banks once. The node block (fused_node_f32.hip)
+// has three H-wide input blocks, K_PAD = 3H + 16, and its own column order;
+// its stride 3H + 20 has the same residue.
 #pragma once
 
 #include <torch/extension.h>
@@ -32,11 +34,16 @@ namespace f32blk {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-template <int H>
+// NBLK: H-wide input blocks ahead of the scalar tail (edge and virtual 2,
+// the node block's [h | agg_e | agg_v] 3, its vel-only form 1). H is a
+// multiple of 32, so K_STRIDE = 20 (mod 32) for every NBLK.
+template <int H, int NBLK = 2>
 struct Dims {
   static_assert(H == 32 || H == 64 || H == 128, "unsupported hidden width");
-  static constexpr int K_PAD = 2 * H + 16;   // roundup16 of 2H+3 .. 2H+9
+  static_assert(NBLK >= 1 && NBLK <= 3, "unsupported input block count");
+  static constexpr int K_PAD = NBLK * H + 16;  // roundup16 of NBLK*H+1 .. +16
   static constexpr int K_STRIDE = K_PAD + 4;
+  static_assert(K_STRIDE % 32 == 20, "float4 fragment reads would conflict");
   static constexpr int NT = H / 16;          // 16-column MFMA tiles per row
   static constexpr int HP = H / 4;           // float4 pieces per H row
   // 64-row tile of four wave sub-tiles; the tile is the only large region:
