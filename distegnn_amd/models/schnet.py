@@ -70,7 +70,6 @@ class CFConv(nn.Module):
                  and x.dtype == torch.bfloat16 and x.size(1) in (64, 128)
                  and sm.offset.numel() <= 64 and rowptr is not None
                  and colptr is not None and ops.hip_ext() is not None
-                 and hasattr(ops.hip_ext(), "cfconv_forward")
                  and os.environ.get("DISTEGNN_DISABLE_FUSED") != "1")
         if fused:
             # one kernel: smearing + filter MLP + cosine cutoff + gathered

@@ -72,8 +72,7 @@ def edge_softmax(scores: torch.Tensor, dst: torch.Tensor,
     h = scores.shape[-1]
     if (csr is not None and scores.is_cuda and scores.dim() == 2
             and 1 <= h <= 64 and (h & (h - 1)) == 0
-            and _ops.hip_ext() is not None
-            and hasattr(_ops.hip_ext(), "edge_softmax_fwd")):
+            and _ops.hip_ext() is not None):
         return _EdgeSoftmaxFn.apply(scores, dst, csr[0], csr[1], num_nodes)
     # segment max for stability
     mx = torch.full((num_nodes,) + scores.shape[1:], -torch.inf,

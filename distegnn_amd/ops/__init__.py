@@ -233,8 +233,7 @@ def virtual_aggregate(v_msg: torch.Tensor, tv: torch.Tensor,
             and ptr is not None and ptr.numel() > 1
             and v_msg.dtype == torch.bfloat16
             and tv.dtype == torch.float32 and tx.dtype == torch.float32
-            and c <= 8 and h % 8 == 0 and h <= 512 and c * h <= 1024
-            and hasattr(hip_ext(), "virtual_aggregate_forward")):
+            and c <= 8 and h % 8 == 0 and h <= 512 and c * h <= 1024):
         cb, ce, scp = chunks
         return _VirtualAggregateFn.apply(v_msg, tv, tx, batch, ptr, cb, ce,
                                          scp)
@@ -280,8 +279,7 @@ class _CoordUpdateFn(torch.autograd.Function):
 def coord_update(coord, agg, trans_v, phiv, vel):
     """coord + agg + trans_v + phi_v * vel, HIP-fused on GPU fp32."""
     if (coord.is_cuda and coord.dtype == torch.float32
-            and hip_ext() is not None
-            and hasattr(hip_ext(), "coord_update_forward")):
+            and hip_ext() is not None):
         return _CoordUpdateFn.apply(coord, agg.float(), trans_v.float(),
                                     phiv.float(), vel)
     return coord + agg + trans_v + phiv * vel
@@ -473,9 +471,9 @@ class _FusedEdgeBlockFn(torch.autograd.Function):
 
     Forward: one HIP kernel produces per-edge msg [M,64] bf16 and
     trans [M,3] f32 (no [M,131]/[M,64] torch intermediates), then the CSR
-    segment-mean kernels aggregate both to nodes. Backward (v1): recompute
-    the eager composition under autograd — its gathers use the CSR
-    segment-sum backward, so no index_add scatters run."""
+    segment-mean kernels aggregate both to nodes. Backward: the fused
+    kernel (csrc/fused_edge_bwd.hip), from node sums of dz1 by default or
+    per edge; or a recompute of the eager composition under autograd."""
 
     @staticmethod
     def forward(ctx, h, coord, eattr, row, col, rowptr, colptr, col_perm,
@@ -503,94 +501,70 @@ class _FusedEdgeBlockFn(torch.autograd.Function):
          w1, b1, w2, b2, w3, b3, w3v) = ctx.saved_tensors
         deg = (rowptr[1:] - rowptr[:-1]).clamp(min=1)
         ext = _load_extension()
-        if ext is not None and os.environ.get(
-                "DISTEGNN_FUSED_BWD_RECOMPUTE") != "1":
-            # fused backward kernel: in-LDS recompute + per-edge grads
-            dmsg_n = (dagg_msg / deg.unsqueeze(-1).to(dagg_msg.dtype)) \
-                .to(torch.bfloat16).contiguous()
-            dtrans_n = (dagg_trans
-                        / deg.unsqueeze(-1).to(dagg_trans.dtype)).contiguous()
-            k_in = w1.size(1)
-            from . import prep
-
-            prepped = [prep.get(w1, "pad_kpad"), prep.get(w1, "tpad_kout"),
-                       prep.get(w2, "bf16"), prep.get(w2, "t_bf16"),
-                       prep.get(w3, "bf16"), prep.get(w3, "t_bf16"),
-                       prep.get(b1, "f32"), prep.get(b2, "f32"),
-                       prep.get(b3, "f32"), prep.get(w3v, "f32")]
-            args = (h, coord, eattr, row, col, dmsg_n, dtrans_n,
-                    w1, b1, w2, b2, w3, b3,
-                    w3v, bool(ctx.normalize), float(ctx.eps), prepped)
-            # measured on MI355X (gpurun_out/r2_call2.log): the wg-fused
-            # kernel eliminates ~2.5 ms/step of split-K wgrad work but its
-            # 68 persistent accumulator VGPRs drop occupancy 3 -> 2
-            # waves/SIMD, costing ~3.4 ms in the backward itself (23.4 ->
-            # 24.3 ms/step net). Off by default until the LDS-phase
-            # pipeline hides enough latency at 2 waves to win.
-            use_wg = (hasattr(ext, "fused_edge_backward_wg")
-                      and h.size(1) == 64
-                      and os.environ.get("DISTEGNN_EDGE_WGRAD_FUSED",
-                                         "0") == "1")
-            # Default: the node-sum path. z1 is linear in ein and ein is
-            # a gather of node rows, so dh and the h-columns of dW1 follow
-            # from S_row/S_col, the per-node sums of dz1 (docs/KERNELS.md):
-            # the kernel stores no ein/dh_row/dh_col and the 1.65M-row
-            # I=144 wgrad becomes N-row products. The per-edge path stays
-            # behind DISTEGNN_EDGE_BWD_PER_EDGE=1 for A/B and accuracy runs.
-            use_lin = (not use_wg and os.environ.get(
-                "DISTEGNN_EDGE_BWD_PER_EDGE", "0") != "1")
-            if use_lin:
-                return _edge_backward_lin(ext, args, h, rowptr, colptr,
-                                          col_perm, w1)
-            if use_wg:
-                # weight gradients accumulated IN the backward kernel (MFMA
-                # accumulators): no [M,144]/[M,64] per-edge intermediates,
-                # no split-K wgrad re-reads
-                (dhr, dhc, dcd, gw3v, gb, gw1, gw2,
-                 gw3) = ext.fused_edge_backward_wg(*args)
-                gw1 = gw1[:, :k_in]
-            else:
-                (ein, t1, msg, dz1, dz2, dz3, dhr, dhc, dcd,
-                 gw3v, gb) = ext.fused_edge_backward(*args)
-            gh = (ext.segment_reduce_csr(dhr, rowptr, False)
-                  + ext.segment_reduce_csr_perm(dhc, colptr, col_perm,
-                                                False))
-            gc = (ext.segment_reduce_csr(dcd, rowptr, False)
-                  - ext.segment_reduce_csr_perm(dcd, colptr, col_perm,
-                                                False))
-            if not use_wg:
-                from . import linear as _lin
-
-                gw1, gw2, gw3 = _lin.grouped_wgrad(
-                    [(dz1, ein), (dz2, t1), (dz3, msg)])
-                gw1 = gw1[:, :k_in].float()
-                gw2 = gw2.float()
-                gw3 = gw3.float()
-            # bias grads accumulated in-kernel (block LDS + atomics):
-            # avoids three aten column-sum re-reads of [M, H]
-            hd = w1.size(0)
-            gb1, gb2, gb3 = gb[:hd], gb[hd:2 * hd], gb[2 * hd:]
-            return (gh.to(h.dtype), gc, None, None, None, None, None, None,
+        if ext is None or os.environ.get(
+                "DISTEGNN_FUSED_BWD_RECOMPUTE") == "1":
+            # recompute the eager composition under autograd
+            dmsg = (dagg_msg / deg.unsqueeze(-1).to(dagg_msg.dtype)) \
+                .index_select(0, row)
+            dtrans = (dagg_trans / deg.unsqueeze(-1).to(dagg_trans.dtype)) \
+                .index_select(0, row)
+            with torch.enable_grad():
+                leaves = [t.detach().requires_grad_(True)
+                          for t in (h, coord, w1, b1, w2, b2, w3, b3, w3v)]
+                hh, cc, lw1, lb1, lw2, lb2, lw3, lb3, lw3v = leaves
+                msg, trans = eager_edge_block(
+                    hh, cc, eattr, row, col, rowptr, colptr, col_perm,
+                    lw1, lb1, lw2, lb2, lw3, lb3, lw3v,
+                    ctx.normalize, ctx.eps)
+                grads = torch.autograd.grad(
+                    (msg, trans), leaves,
+                    grad_outputs=(dmsg.to(msg.dtype), dtrans.to(trans.dtype)),
+                    allow_unused=True)
+            gh, gc, gw1, gb1, gw2, gb2, gw3, gb3, gw3v = grads
+            return (gh, gc, None, None, None, None, None, None,
                     gw1, gb1, gw2, gb2, gw3, gb3, gw3v, None, None)
-        # fallback: recompute the eager composition under autograd
-        dmsg = (dagg_msg / deg.unsqueeze(-1).to(dagg_msg.dtype)) \
-            .index_select(0, row)
-        dtrans = (dagg_trans / deg.unsqueeze(-1).to(dagg_trans.dtype)) \
-            .index_select(0, row)
-        with torch.enable_grad():
-            leaves = [t.detach().requires_grad_(True)
-                      for t in (h, coord, w1, b1, w2, b2, w3, b3, w3v)]
-            hh, cc, lw1, lb1, lw2, lb2, lw3, lb3, lw3v = leaves
-            msg, trans = eager_edge_block(
-                hh, cc, eattr, row, col, rowptr, colptr, col_perm,
-                lw1, lb1, lw2, lb2, lw3, lb3, lw3v,
-                ctx.normalize, ctx.eps)
-            grads = torch.autograd.grad(
-                (msg, trans), leaves,
-                grad_outputs=(dmsg.to(msg.dtype), dtrans.to(trans.dtype)),
-                allow_unused=True)
-        gh, gc, gw1, gb1, gw2, gb2, gw3, gb3, gw3v = grads
-        return (gh, gc, None, None, None, None, None, None,
+        # fused backward kernel: in-LDS recompute + per-edge grads
+        dmsg_n = (dagg_msg / deg.unsqueeze(-1).to(dagg_msg.dtype)) \
+            .to(torch.bfloat16).contiguous()
+        dtrans_n = (dagg_trans
+                    / deg.unsqueeze(-1).to(dagg_trans.dtype)).contiguous()
+        from . import prep
+
+        prepped = [prep.get(w1, "pad_kpad"), prep.get(w1, "tpad_kout"),
+                   prep.get(w2, "bf16"), prep.get(w2, "t_bf16"),
+                   prep.get(w3, "bf16"), prep.get(w3, "t_bf16"),
+                   prep.get(b1, "f32"), prep.get(b2, "f32"),
+                   prep.get(b3, "f32"), prep.get(w3v, "f32")]
+        args = (h, coord, eattr, row, col, dmsg_n, dtrans_n,
+                w1, b1, w2, b2, w3, b3,
+                w3v, bool(ctx.normalize), float(ctx.eps), prepped)
+        # Default: the node-sum path. z1 is linear in ein and ein is
+        # a gather of node rows, so dh and the h-columns of dW1 follow
+        # from S_row/S_col, the per-node sums of dz1 (docs/KERNELS.md):
+        # the kernel stores no ein/dh_row/dh_col and the 1.65M-row
+        # I=144 wgrad becomes N-row products. The per-edge path stays
+        # behind DISTEGNN_EDGE_BWD_PER_EDGE=1 for A/B and accuracy runs.
+        if os.environ.get("DISTEGNN_EDGE_BWD_PER_EDGE", "0") != "1":
+            return _edge_backward_lin(ext, args, h, rowptr, colptr,
+                                      col_perm, w1)
+        (ein, t1, msg, dz1, dz2, dz3, dhr, dhc, dcd,
+         gw3v, gb) = ext.fused_edge_backward(*args)
+        gh = (ext.segment_reduce_csr(dhr, rowptr, False)
+              + ext.segment_reduce_csr_perm(dhc, colptr, col_perm, False))
+        gc = (ext.segment_reduce_csr(dcd, rowptr, False)
+              - ext.segment_reduce_csr_perm(dcd, colptr, col_perm, False))
+        from . import linear as _lin
+
+        gw1, gw2, gw3 = _lin.grouped_wgrad(
+            [(dz1, ein), (dz2, t1), (dz3, msg)])
+        gw1 = gw1[:, :w1.size(1)].float()
+        gw2 = gw2.float()
+        gw3 = gw3.float()
+        # bias grads accumulated in-kernel (block LDS + atomics):
+        # avoids three aten column-sum re-reads of [M, H]
+        hd = w1.size(0)
+        gb1, gb2, gb3 = gb[:hd], gb[hd:2 * hd], gb[2 * hd:]
+        return (gh.to(h.dtype), gc, None, None, None, None, None, None,
                 gw1, gb1, gw2, gb2, gw3, gb3, gw3v, None, None)
 
 
@@ -673,27 +647,6 @@ def _no_grad_needed(*tensors):
                 and any(t.requires_grad for t in tensors))
 
 
-def _edge_fallback_reason(h, eattr, rowptr, colptr, col_perm,
-                          dtype_ok=None):
-    if not h.is_cuda or hip_ext() is None:
-        return None            # CPU / no extension: expected, don't warn
-    if os.environ.get("DISTEGNN_DISABLE_FUSED") == "1":
-        return None            # explicit opt-out
-    if dtype_ok is None:
-        dtype_ok = h.dtype == torch.bfloat16
-    if not dtype_ok:
-        return _dtype_fallback_reason(h.dtype)
-    if h.size(1) not in (32, 64, 128):
-        return (f"hidden_nf={h.size(1)} (the edge kernels are compiled "
-                f"for H in {{32, 64, 128}})")
-    if eattr is None or eattr.size(1) != 2:
-        return (f"edge_attr_nf="
-                f"{0 if eattr is None else eattr.size(1)} (kernels expect 2)")
-    if rowptr is None or colptr is None or col_perm is None:
-        return "batch lacks CSR metadata (rowptr/colptr/col_perm)"
-    return None
-
-
 def _edge_block_f32(h, coord, eattr, row, col, rowptr, params, normalize,
                     eps):
     """Forward-only fp32 edge block: csrc/fused_edge_f32.hip, then the CSR
@@ -722,30 +675,32 @@ def fused_edge_block(h, coord, eattr, row, col, rowptr, colptr, col_perm,
 
     Returns (agg_msg [N,H], agg_trans [N,3]) — per-node MEANS of the edge
     messages and coordinate translations."""
-    shape_ok = (h.is_cuda and h.size(1) in (32, 64, 128)
-                and eattr is not None and eattr.size(1) == 2
-                and rowptr is not None and colptr is not None
-                and col_perm is not None and hip_ext() is not None
-                and os.environ.get("DISTEGNN_DISABLE_FUSED") != "1")
-    if shape_ok and h.dtype == torch.bfloat16:
-        return _FusedEdgeBlockFn.apply(
-            h, coord, eattr, row, col, rowptr, colptr, col_perm,
-            w1, b1, w2, b2, w3, b3, w3v, normalize, eps)
-    params = (w1, b1, w2, b2, w3, b3, w3v)
-    f32_fwd = (h.is_cuda
-               and all(t.dtype == torch.float32
+    if (h.is_cuda and hip_ext() is not None
+            and os.environ.get("DISTEGNN_DISABLE_FUSED") != "1"):
+        params = (w1, b1, w2, b2, w3, b3, w3v)
+        f32_fwd = (all(t.dtype == torch.float32
                        for t in (h, coord, eattr) + params
                        if t is not None)
-               and hasattr(hip_ext(), "fused_edge_forward_f32")
-               and _no_grad_needed(h, coord, *params))
-    if shape_ok and f32_fwd:
-        return _edge_block_f32(h, coord, eattr, row, col, rowptr, params,
-                               normalize, eps)
-    reason = _edge_fallback_reason(h, eattr, rowptr, colptr, col_perm,
-                                   dtype_ok=bool(
-                                       f32_fwd
-                                       or h.dtype == torch.bfloat16))
-    if reason is not None:
+                   and _no_grad_needed(h, coord, *params))
+        reason = None
+        if h.dtype != torch.bfloat16 and not f32_fwd:
+            reason = _dtype_fallback_reason(h.dtype)
+        elif h.size(1) not in (32, 64, 128):
+            reason = (f"hidden_nf={h.size(1)} (the edge kernels are compiled "
+                      f"for H in {{32, 64, 128}})")
+        elif eattr is None or eattr.size(1) != 2:
+            reason = (f"edge_attr_nf="
+                      f"{0 if eattr is None else eattr.size(1)} "
+                      f"(kernels expect 2)")
+        elif rowptr is None or colptr is None or col_perm is None:
+            reason = "batch lacks CSR metadata (rowptr/colptr/col_perm)"
+        if reason is None and f32_fwd:
+            return _edge_block_f32(h, coord, eattr, row, col, rowptr, params,
+                                   normalize, eps)
+        if reason is None:
+            return _FusedEdgeBlockFn.apply(
+                h, coord, eattr, row, col, rowptr, colptr, col_perm,
+                w1, b1, w2, b2, w3, b3, w3v, normalize, eps)
         _warn_fallback("fused_edge_block", reason)
     msg, trans = eager_edge_block(
         h, coord, eattr, row, col, rowptr, colptr, col_perm,
@@ -902,33 +857,14 @@ def fused_virtual_block(h, coord, vcoord, vfeat, gram, batch, ptr, chunks,
 
     Returns (v_msg [N,C,H], tv [N,C,3], tx [N,C,3]); the model derives
     trans_v = tv.mean(1), agg_v = v_msg.mean(1), and pools tx / v_msg."""
-    shape_ok = (h.is_cuda and h.size(1) in _VIRTUAL_H
-                and vcoord.size(1) <= 8 and ptr is not None
-                and hip_ext() is not None
-                and os.environ.get("DISTEGNN_DISABLE_FUSED") != "1")
-    usable = shape_ok and h.dtype == torch.bfloat16
-    params = (w1, b1, w2, b2, wxv, bxv, wxvv, wX, bX, wXv)
-    # forward-only fp32 kernel (csrc/fused_virtual_f32.hip) when no
-    # gradient is needed
-    f32_fwd = (h.is_cuda
-               and all(t.dtype == torch.float32
-                       for t in (h, coord, vcoord, vfeat, gram) + params)
-               and hasattr(hip_ext(), "fused_virtual_forward_f32")
-               and _no_grad_needed(h, coord, vcoord, vfeat, gram, *params))
-    if shape_ok and not usable and f32_fwd:
-        from . import prep
-
-        with torch.no_grad():
-            prepped = [prep.get(t, "frag16_f32")
-                       for t in (w1, w2, wxv, wX)] + [
-                prep.get(t, "f32") for t in (b1, b2, bxv, bX, wxvv, wXv)]
-            vmsg, tv, tx = hip_ext().fused_virtual_forward_f32(
-                h, coord, vcoord, vfeat, gram, batch, w1, b1, w2, b2, wxv,
-                bxv, wxvv, wX, bX, wXv, prepped)
-        n, c = h.size(0), vcoord.size(1)
-        return vmsg.view(n, c, -1), tv.view(n, c, 3), tx.view(n, c, 3)
-    if (not usable and h.is_cuda and hip_ext() is not None
+    if (h.is_cuda and hip_ext() is not None
             and os.environ.get("DISTEGNN_DISABLE_FUSED") != "1"):
+        params = (w1, b1, w2, b2, wxv, bxv, wxvv, wX, bX, wXv)
+        f32_fwd = (all(t.dtype == torch.float32
+                       for t in (h, coord, vcoord, vfeat, gram) + params)
+                   and _no_grad_needed(h, coord, vcoord, vfeat, gram,
+                                       *params))
+        reason = None
         if h.dtype != torch.bfloat16 and not f32_fwd:
             reason = _dtype_fallback_reason(h.dtype)
         elif h.size(1) not in _VIRTUAL_H:
@@ -936,20 +872,33 @@ def fused_virtual_block(h, coord, vcoord, vfeat, gram, batch, ptr, chunks,
                       f"compiled for H in {{32, 64, 128}})")
         elif vcoord.size(1) > 8:
             reason = f"virtual_channels={vcoord.size(1)} (kernels cover <=8)"
-        else:
+        elif ptr is None:
             reason = "batch lacks graph ptr metadata"
+        if reason is None and f32_fwd:
+            # forward-only fp32 kernel (csrc/fused_virtual_f32.hip)
+            from . import prep
+
+            with torch.no_grad():
+                prepped = [prep.get(t, "frag16_f32")
+                           for t in (w1, w2, wxv, wX)] + [
+                    prep.get(t, "f32") for t in (b1, b2, bxv, bX, wxvv, wXv)]
+                vmsg, tv, tx = hip_ext().fused_virtual_forward_f32(
+                    h, coord, vcoord, vfeat, gram, batch, w1, b1, w2, b2, wxv,
+                    bxv, wxvv, wX, bX, wXv, prepped)
+            n, c = h.size(0), vcoord.size(1)
+            return vmsg.view(n, c, -1), tv.view(n, c, 3), tx.view(n, c, 3)
+        if reason is None:
+            cb, ce, scp = chunks if chunks is not None else (None, None, None)
+            empty = batch.new_empty(0)
+            train = torch.is_grad_enabled() and (
+                h.requires_grad or w1.requires_grad or coord.requires_grad)
+            return _FusedVirtualBlockFn.apply(
+                h, coord, vcoord, vfeat, gram, batch, ptr,
+                cb if cb is not None else empty,
+                ce if ce is not None else empty,
+                scp if scp is not None else empty,
+                w1, b1, w2, b2, wxv, bxv, wxvv, wX, bX, wXv, train)
         _warn_fallback("fused_virtual_block", reason)
-    if usable:
-        cb, ce, scp = chunks if chunks is not None else (None, None, None)
-        empty = batch.new_empty(0)
-        train = torch.is_grad_enabled() and (
-            h.requires_grad or w1.requires_grad or coord.requires_grad)
-        return _FusedVirtualBlockFn.apply(
-            h, coord, vcoord, vfeat, gram, batch, ptr,
-            cb if cb is not None else empty,
-            ce if ce is not None else empty,
-            scp if scp is not None else empty,
-            w1, b1, w2, b2, wxv, bxv, wxvv, wX, bX, wXv, train)
     return eager_virtual_block(h, coord, vcoord, vfeat, gram, batch,
                                w1, b1, w2, b2, wxv, bxv, wxvv, wX, bX, wXv)
 
@@ -1128,10 +1077,6 @@ def fused_node_block(h, agg_e, agg_v, attr, node_mlp, vel_mlp, residual=True,
                  or os.environ.get("DISTEGNN_NODE_EAGER") == "1")
     reason = None
     if h.is_cuda and hip_ext() is not None and not opted_out:
-        if not hasattr(hip_ext(), "fused_node_forward"):
-            raise RuntimeError(
-                "distegnn_amd HIP extension lacks fused_node_forward; "
-                "rebuild it (python -m distegnn_amd.ops.build)")
         # fp32 tensors the block would read: a candidate for the
         # forward-only fp32 kernel when no gradient is needed
         used = [h] if vel_only else [
@@ -1140,9 +1085,7 @@ def fused_node_block(h, agg_e, agg_v, attr, node_mlp, vel_mlp, residual=True,
         if not vel_only:
             used += list(node_mlp.parameters())
         all_f32 = all(t.dtype == torch.float32 for t in used)
-        f32_fwd = (all_f32
-                   and hasattr(hip_ext(), "fused_node_forward_f32")
-                   and _no_grad_needed(*used))
+        f32_fwd = all_f32 and _no_grad_needed(*used)
         widths = _NODE_H_F32 if f32_fwd else _NODE_H
         if h.dtype == torch.float32 and not all_f32:
             reason = ("dtype torch.float32 with an input or parameter of "

@@ -2,10 +2,11 @@
 //
 // Recomputes the forward chain tile-by-tile (checkpoint style) and emits
 // every per-edge gradient in ONE kernel. See fused_edge.hip for the chain;
-// the python side finishes with three split-K wgrad GEMMs, bias column
-// sums and CSR segment sums (ops/__init__.py _FusedEdgeBlockFn.backward).
-// The default mode, EB_LIN below, leaves dh and the h-columns of dW1 to
-// per-node sums of dz1 and emits neither ein nor dh_row / dh_col.
+// the python side finishes with three split-K wgrad GEMMs and CSR segment
+// sums (ops/__init__.py _FusedEdgeBlockFn.backward); the bias column sums
+// are taken here. Two modes: per edge (EB_PLAIN) stores ein and
+// dh_row / dh_col; the default, EB_LIN below, leaves dh and the h-columns of
+// dW1 to per-node sums of dz1 and emits none of the three.
 //
 // Occupancy design (PMC-driven, same as the forward): weights are read
 // from GLOBAL padded/transposed copies (L2-resident) instead of LDS, and
@@ -117,55 +118,6 @@ __device__ __forceinline__ bf16x8 lds8_silu(const char* smem, int off) {
   return r;
 }
 
-// Transposed fragment: A[i][k] = T[k][i] for a row-major LDS tile
-// T[edge][c] with byte stride `stride` — 8 strided u16 reads per lane.
-// Used by the in-kernel wgrad GEMMs, whose contraction runs over the
-// EDGE dimension (the tile row index).
-__device__ __forceinline__ bf16x8 lds8_t(const char* smem, int base,
-                                         int stride, int i, int k0) {
-  bf16x8 v;
-#pragma unroll
-  for (int u = 0; u < 8; ++u)
-    v[u] = *reinterpret_cast<const __bf16*>(smem + base +
-                                            (k0 + u) * stride + i * 2);
-  return v;
-}
-__device__ __forceinline__ bf16x8 lds8_t_silu(const char* smem, int base,
-                                              int stride, int i, int k0) {
-  bf16x8 v = lds8_t(smem, base, stride, i, k0);
-#pragma unroll
-  for (int u = 0; u < 8; ++u) v[u] = (__bf16)silu_((float)v[u]);
-  return v;
-}
-
-// In-kernel weight-gradient accumulation: dW[i][j] += sum_e dz[e][i] *
-// act[e][j] over this tile's 64 edges (2 MFMA k-steps). Each wave owns
-// i-tile `wave`; NJ j-tiles; padded edges contribute zero because their
-// dz rows are exactly zero.
-template <int NJ, bool SILU_B>
-__device__ __forceinline__ void wg_acc(const char* smem, int a_base,
-                                       int a_stride, int b_base,
-                                       int b_stride, int wave, int lane,
-                                       f32x4 (&acc)[NJ]) {
-__builtin_amdgcn_s_setprio(1);
-  #pragma unroll
-  for (int kk = 0; kk < 2; ++kk) {
-    int k0 = kk * 32 + (lane >> 4) * 8;
-    bf16x8 a = lds8_t(smem, a_base, a_stride, wave * 16 + (lane & 15), k0);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      bf16x8 b = SILU_B
-                     ? lds8_t_silu(smem, b_base, b_stride,
-                                   j * 16 + (lane & 15), k0)
-                     : lds8_t(smem, b_base, b_stride, j * 16 + (lane & 15),
-                              k0);
-      acc[j] =
-          __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[j], 0, 0, 0);
-    }
-  }
-  __builtin_amdgcn_s_setprio(0);
-}
-
 // A from LDS (optionally through silu), B from global [64][wk] k-contig.
 template <int KSTEPS, bool SILU_A, int NT>
 __device__ __forceinline__ void mm_g(const char* smem, int a_off,
@@ -187,14 +139,6 @@ __builtin_amdgcn_s_setprio(1);
   __builtin_amdgcn_s_setprio(0);
 }
 
-// FUSE_WG: accumulate the three weight gradients (dW1 = dz1^T ein,
-// dW2 = dz2^T silu(z1), dW3 = dz3^T silu(z2)) in MFMA accumulator
-// registers INSIDE this kernel and skip materializing ein/t1/msg/dz1/
-// dz2/dz3 to global (~1.2 KB/edge of stores whose only consumers were
-// the split-K wgrad kernels re-reading them). Costs 68 persistent
-// VGPRs -> 2 waves/SIMD instead of 3; saves the whole wgrad kernel
-// family plus the traffic.
-//
 // EB_LIN: the first layer is linear in ein and ein is a gather of node
 // rows, so dh and the h-columns of dW1 follow from per-node sums of dz1
 // (S_row, S_col; see docs/KERNELS.md). This mode stores neither ein nor
@@ -205,12 +149,11 @@ __builtin_amdgcn_s_setprio(1);
 // over a wave's 16 rows in a fixed order and stored as one partial row per
 // (tile, wave). The host folds the partial rows with a deterministic sum,
 // so dW1 is bit-identical run to run (no atomics on a weight gradient).
-enum EdgeBwdMode { EB_PLAIN = 0, EB_FUSE_WG = 1, EB_LIN = 2 };
+enum EdgeBwdMode { EB_PLAIN = 0, EB_LIN = 1 };
 
 template <int H, int MODE>
 __global__ __launch_bounds__(THREADS,
-                             MODE == EB_FUSE_WG ? 2
-                             : (MODE == EB_LIN && H == 32) ? 4
+                             (MODE == EB_LIN && H == 32) ? 4
                              : (H <= 64 ? 3 : 1))
 void fused_edge_bwd(
     const bf16* __restrict__ h, const float* __restrict__ coord,
@@ -230,15 +173,9 @@ void fused_edge_bwd(
     bf16* __restrict__ dhr_out, bf16* __restrict__ dhc_out,
     float* __restrict__ dcd_out, float* __restrict__ dw3v_out,
     float* __restrict__ gb_out,  // [3*H]: gb1 | gb2 | gb3 column sums
-    float* __restrict__ gw1_out,  // FUSE_WG: [H][K_OUT]
-                                  // LIN: tail partials [4*ntile][3*H]
-    float* __restrict__ gw2_out,  // [H][H]
-    float* __restrict__ gw3_out,  // [H][H]
+    float* __restrict__ tail_out,  // LIN: dW1 tail partials [4*ntile][3*H]
     long m, int normalize, float eps) {
-  constexpr bool FUSE_WG = MODE == EB_FUSE_WG;
   constexpr bool LIN = MODE == EB_LIN;
-  static_assert(!FUSE_WG || H == 64,
-                "the wgrad-fused variant is tuned for H=64 only");
   constexpr int K_IN = EDB<H>::K_IN;
   constexpr int K_PAD = EDB<H>::K_PAD;
   constexpr int K_STRIDE = EDB<H>::K_STRIDE;
@@ -252,10 +189,6 @@ void fused_edge_bwd(
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
-  // per-wave wgrad accumulators (i-tile = wave), live across the tile loop
-  f32x4 wg1[9] = {};
-  f32x4 wg2[4] = {};
-  f32x4 wg3[4] = {};
 
   float* biases = reinterpret_cast<float*>(smem + L.bias);
   float* wpart = reinterpret_cast<float*>(smem + L.wpart);
@@ -272,13 +205,13 @@ void fused_edge_bwd(
   }
   __syncthreads();  // biases/accumulators initialized by wave 0
 
-  // Wave-per-subtile execution (round 2): every phase below reads and
-  // writes ONLY its own wave's 16 rows of each LDS tile, so the plain
-  // variant needs NO intra-tile barriers at all — 12 independent waves
-  // per CU instead of 3 barrier-convoyed 4-wave groups (PMC showed 62%
-  // SQ_WAIT_ANY dominated by the 14 sync-separated phases). The FUSE_WG
-  // variant's wgrad contraction runs over the whole 64-edge tile, so it
-  // keeps the original barrier schedule.
+  // Wave-per-subtile execution: every phase below reads and writes ONLY
+  // its own wave's 16 rows of each LDS tile (and its own 16 entries of
+  // rows/cols/diff/scal), so the tile loop needs NO barriers in either
+  // mode — 12 independent waves per CU instead of 3 barrier-convoyed
+  // 4-wave groups (PMC showed 62% SQ_WAIT_ANY dominated by the 14
+  // sync-separated phases). The block-wide wpart/gbacc sums are LDS
+  // atomics, flushed after the one barrier that follows the loop.
   // XCD-aware tile remap (same as fused_edge_fwd): contiguous tile
   // ranges per XCD keep each XCD's row gathers inside its 4 MiB L2.
   const long ntile = (m + TILE - 1) / TILE;
@@ -289,7 +222,6 @@ void fused_edge_bwd(
         (xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq) + ti;
     long e0 = tile * TILE;
     int nedge = (int)((m - e0 < (long)TILE) ? (m - e0) : (long)TILE);
-    if constexpr (FUSE_WG) __syncthreads();
     int* rws = reinterpret_cast<int*>(smem + L.rows);
     int* cls = reinterpret_cast<int*>(smem + L.cols);
     if (lane < 16) {
@@ -297,7 +229,6 @@ void fused_edge_bwd(
       rws[e] = e < nedge ? (int)row[e0 + e] : 0;
       cls[e] = e < nedge ? (int)col[e0 + e] : 0;
     }
-    if constexpr (FUSE_WG) __syncthreads();
 
     // ---- stage ein (wave-local rows) ----
     for (int idx = lane; idx < 16 * 2 * HP; idx += 64) {
@@ -334,9 +265,8 @@ void fused_edge_bwd(
 #pragma unroll
       for (int k = K_IN; k < K_PAD; ++k) brow[k] = (__bf16)0.f;
     }
-    if constexpr (FUSE_WG) __syncthreads();
     // ein -> global (only the split-K wgrad path consumes it)
-    if constexpr (MODE == EB_PLAIN) {
+    if constexpr (!LIN) {
       for (int idx = lane; idx < 16 * (K_OUT / 8); idx += 64) {
         int e = wave * 16 + idx / (K_OUT / 8);
         if (e >= nedge) continue;
@@ -362,16 +292,13 @@ void fused_edge_bwd(
         }
       }
     }
-    if constexpr (FUSE_WG) __syncthreads();
     // t1 = silu(z1) -> global (coalesced, wave-local rows)
-    if constexpr (!FUSE_WG) {
-      for (int idx = lane; idx < 16 * HP; idx += 64) {
-        int e = wave * 16 + idx / HP;
-        if (e >= nedge) continue;
-        int c8 = (idx % HP) * 8;
-        *reinterpret_cast<bf16x8*>(t1_out + (e0 + e) * H + c8) =
-            lds8_silu(smem, L.z1 + (e * H_STRIDE + c8) * 2);
-      }
+    for (int idx = lane; idx < 16 * HP; idx += 64) {
+      int e = wave * 16 + idx / HP;
+      if (e >= nedge) continue;
+      int c8 = (idx % HP) * 8;
+      *reinterpret_cast<bf16x8*>(t1_out + (e0 + e) * H + c8) =
+          lds8_silu(smem, L.z1 + (e * H_STRIDE + c8) * 2);
     }
     {
       f32x4 acc[NT] = {};
@@ -388,15 +315,12 @@ void fused_edge_bwd(
         }
       }
     }
-    if constexpr (FUSE_WG) __syncthreads();
-    if constexpr (!FUSE_WG) {
-      for (int idx = lane; idx < 16 * HP; idx += 64) {
-        int e = wave * 16 + idx / HP;
-        if (e >= nedge) continue;
-        int c8 = (idx % HP) * 8;
-        *reinterpret_cast<bf16x8*>(msg_out + (e0 + e) * H + c8) =
-            lds8_silu(smem, L.z2 + (e * H_STRIDE + c8) * 2);
-      }
+    for (int idx = lane; idx < 16 * HP; idx += 64) {
+      int e = wave * 16 + idx / HP;
+      if (e >= nedge) continue;
+      int c8 = (idx % HP) * 8;
+      *reinterpret_cast<bf16x8*>(msg_out + (e0 + e) * H + c8) =
+          lds8_silu(smem, L.z2 + (e * H_STRIDE + c8) * 2);
     }
     {
       f32x4 acc[NT] = {};
@@ -427,7 +351,6 @@ void fused_edge_bwd(
           sc[(wave * 16 + (lane >> 4) * 4 + r) * 4] = part[r];  // p
       }
     }
-    if constexpr (FUSE_WG) __syncthreads();
 
     // ---- head backward: dp; dw3v partial; dz3 overwrites z3 ----
     if (lane < 16) {
@@ -443,7 +366,6 @@ void fused_edge_bwd(
       }
       sc[1] = dp;
     }
-    if constexpr (FUSE_WG) __syncthreads();
 #pragma unroll
     for (int c = tid & 63; c < H; c += 64) {
       // lane covers column(s) c over its wave's 16 edges: dw3v partial +
@@ -464,21 +386,12 @@ void fused_edge_bwd(
       atomicAdd(&wpart[c], acc_w);
       atomicAdd(&gbacc[2 * H + c], acc_b3);
     }
-    if constexpr (FUSE_WG) __syncthreads();
-    if constexpr (FUSE_WG) {
-      // dW3 += dz3^T (in z3) @ silu(z2): z3 is consumed below (dmsg
-      // staging overwrites it only after a barrier every wave reaches
-      // after this accumulation)
-      wg_acc<4, true>(smem, L.z3, H_STRIDE * 2, L.z2, H_STRIDE * 2, wave,
-                      lane, wg3);
-    } else {
-      for (int idx = lane; idx < 16 * HP; idx += 64) {
-        int e = wave * 16 + idx / HP;
-        if (e >= nedge) continue;
-        int c8 = (idx % HP) * 8;
-        *reinterpret_cast<bf16x8*>(dz3_out + (e0 + e) * H + c8) =
-            lds8(smem, L.z3 + (e * H_STRIDE + c8) * 2);
-      }
+    for (int idx = lane; idx < 16 * HP; idx += 64) {
+      int e = wave * 16 + idx / HP;
+      if (e >= nedge) continue;
+      int c8 = (idx % HP) * 8;
+      *reinterpret_cast<bf16x8*>(dz3_out + (e0 + e) * H + c8) =
+          lds8(smem, L.z3 + (e * H_STRIDE + c8) * 2);
     }
 
     // ---- dz2 = (dmsg_n[row] + dz3 @ W3) silu'(z2), overwrite z2 ----
@@ -486,7 +399,6 @@ void fused_edge_bwd(
       f32x4 acc[NT] = {};
       mm_g<H / 32, false, NT>(smem, L.z3 + wave * 16 * H_STRIDE * 2, H_STRIDE * 2,
                      opaque(w3t), H, lane, acc);
-      if constexpr (FUSE_WG) __syncthreads();
       // z3 consumed: reuse its tile to stage dmsg_n[row] COALESCED
       // (the C-layout merge otherwise issues 16 scattered 2 B loads/lane)
       for (int idx = lane; idx < 16 * HP; idx += 64) {
@@ -496,7 +408,6 @@ void fused_edge_bwd(
         if (e < nedge) v = g8(dmsg_n + (long)rws[e] * H + c8);
         *reinterpret_cast<bf16x8*>(smem + L.z3 + (e * H_STRIDE + c8) * 2) = v;
       }
-      if constexpr (FUSE_WG) __syncthreads();
       __bf16* z2 = reinterpret_cast<__bf16*>(smem + L.z2);
       const __bf16* dmsg_t = reinterpret_cast<const __bf16*>(smem + L.z3);
 #pragma unroll
@@ -511,20 +422,12 @@ void fused_edge_bwd(
         }
       }
     }
-    if constexpr (FUSE_WG) __syncthreads();
-    if constexpr (FUSE_WG) {
-      // dW2 += dz2^T (in z2) @ silu(z1): z1 still holds pre-activations
-      // (overwritten only after the barrier inside the dz1 phase)
-      wg_acc<4, true>(smem, L.z2, H_STRIDE * 2, L.z1, H_STRIDE * 2, wave,
-                      lane, wg2);
-    } else {
-      for (int idx = lane; idx < 16 * HP; idx += 64) {
-        int e = wave * 16 + idx / HP;
-        if (e >= nedge) continue;
-        int c8 = (idx % HP) * 8;
-        *reinterpret_cast<bf16x8*>(dz2_out + (e0 + e) * H + c8) =
-            lds8(smem, L.z2 + (e * H_STRIDE + c8) * 2);
-      }
+    for (int idx = lane; idx < 16 * HP; idx += 64) {
+      int e = wave * 16 + idx / HP;
+      if (e >= nedge) continue;
+      int c8 = (idx % HP) * 8;
+      *reinterpret_cast<bf16x8*>(dz2_out + (e0 + e) * H + c8) =
+          lds8(smem, L.z2 + (e * H_STRIDE + c8) * 2);
     }
 #pragma unroll
     for (int c = tid & 63; c < H; c += 64) {
@@ -541,7 +444,6 @@ void fused_edge_bwd(
       f32x4 acc[NT] = {};
       mm_g<H / 32, false, NT>(smem, L.z2 + wave * 16 * H_STRIDE * 2, H_STRIDE * 2,
                      opaque(w2t), H, lane, acc);
-      if constexpr (FUSE_WG) __syncthreads();
       __bf16* z1 = reinterpret_cast<__bf16*>(smem + L.z1);
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
@@ -554,15 +456,12 @@ void fused_edge_bwd(
         }
       }
     }
-    if constexpr (FUSE_WG) __syncthreads();
-    if constexpr (!FUSE_WG) {
-      for (int idx = lane; idx < 16 * HP; idx += 64) {
-        int e = wave * 16 + idx / HP;
-        if (e >= nedge) continue;
-        int c8 = (idx % HP) * 8;
-        *reinterpret_cast<bf16x8*>(dz1_out + (e0 + e) * H + c8) =
-            lds8(smem, L.z1 + (e * H_STRIDE + c8) * 2);
-      }
+    for (int idx = lane; idx < 16 * HP; idx += 64) {
+      int e = wave * 16 + idx / HP;
+      if (e >= nedge) continue;
+      int c8 = (idx % HP) * 8;
+      *reinterpret_cast<bf16x8*>(dz1_out + (e0 + e) * H + c8) =
+          lds8(smem, L.z1 + (e * H_STRIDE + c8) * 2);
     }
 #pragma unroll
     for (int c = tid & 63; c < H; c += 64) {
@@ -572,14 +471,6 @@ void fused_edge_bwd(
       for (int e = estart; e < estart + 16; ++e)
         acc_b += (float)z1[e * H_STRIDE + c];
       atomicAdd(&gbacc[c], acc_b);
-    }
-    if constexpr (FUSE_WG) {
-      // dW1 += dz1^T (in z1) @ ein (still in in_tile; K_OUT-col range is
-      // zero-padded past K_IN). Must fully drain before the dein passes
-      // overwrite in_tile -> barrier.
-      wg_acc<9, false>(smem, L.z1, H_STRIDE * 2, L.in_tile, K_STRIDE * 2,
-                       wave, lane, wg1);
-      __syncthreads();
     }
 
     // ---- dein = dz1 @ W1 in register passes of <=3 n-tiles ----
@@ -610,7 +501,7 @@ void fused_edge_bwd(
       // rows, as is dz1), so each product is exact in fp32. Lane c sums
       // column c over its wave's 16 rows in order; every (tile, wave)
       // writes its whole partial row.
-      float* tl = gw1_out +
+      float* tl = tail_out +
                   ((e0 >> 6) * 4 + __builtin_amdgcn_readfirstlane(wave)) *
                       (3 * H);
 #pragma unroll
@@ -666,7 +557,6 @@ void fused_edge_bwd(
         }
       }
     }
-    if constexpr (FUSE_WG) __syncthreads();
     // dh_row / dh_col -> global (coalesced, wave-local rows)
     if constexpr (!LIN) {
       for (int idx = lane; idx < 16 * HP; idx += 64) {
@@ -698,24 +588,6 @@ void fused_edge_bwd(
   __syncthreads();
   for (int c = tid; c < H; c += THREADS) atomicAdd(&dw3v_out[c], wpart[c]);
   for (int c = tid; c < 3 * H; c += THREADS) atomicAdd(&gb_out[c], gbacc[c]);
-  if constexpr (FUSE_WG) {
-    // flush wgrad accumulators: D fragment row = (lane>>4)*4 + r,
-    // col = lane & 15; wave owns i-tile `wave`.
-    int i = wave * 16 + (lane >> 4) * 4;
-    int j0 = lane & 15;
-#pragma unroll
-    for (int jt = 0; jt < 9; ++jt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        atomicAdd(&gw1_out[(i + r) * K_OUT + jt * 16 + j0], wg1[jt][r]);
-#pragma unroll
-    for (int jt = 0; jt < 4; ++jt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        atomicAdd(&gw2_out[(i + r) * H + jt * 16 + j0], wg2[jt][r]);
-        atomicAdd(&gw3_out[(i + r) * H + jt * 16 + j0], wg3[jt][r]);
-      }
-  }
 }
 
 }  // namespace
@@ -728,7 +600,6 @@ static std::vector<torch::Tensor> fused_edge_backward_impl(
     torch::Tensor w2, torch::Tensor b2, torch::Tensor w3, torch::Tensor b3,
     torch::Tensor w3v, bool normalize, double eps,
     std::vector<torch::Tensor> prepped) {
-  constexpr bool FUSE_WG = MODE == EB_FUSE_WG;
   constexpr bool LIN = MODE == EB_LIN;
   long m = row.numel();
   constexpr int K_IN = EDB<H>::K_IN;
@@ -736,13 +607,12 @@ static std::vector<torch::Tensor> fused_edge_backward_impl(
   constexpr int K_OUT = EDB<H>::K_OUT;
   auto bopt = h.options();
   auto fopt = coord.options().dtype(torch::kFloat);
-  long edge_rows = FUSE_WG ? 0 : m;  // per-edge buffers only when needed
-  auto ein = torch::empty({LIN ? 0 : edge_rows, (long)K_OUT}, bopt);
-  auto t1 = torch::empty({edge_rows, (long)H}, bopt);
-  auto msg = torch::empty({edge_rows, (long)H}, bopt);
-  auto dz1 = torch::empty({edge_rows, (long)H}, bopt);
-  auto dz2 = torch::empty({edge_rows, (long)H}, bopt);
-  auto dz3 = torch::empty({edge_rows, (long)H}, bopt);
+  auto ein = torch::empty({LIN ? 0 : m, (long)K_OUT}, bopt);
+  auto t1 = torch::empty({m, (long)H}, bopt);
+  auto msg = torch::empty({m, (long)H}, bopt);
+  auto dz1 = torch::empty({m, (long)H}, bopt);
+  auto dz2 = torch::empty({m, (long)H}, bopt);
+  auto dz3 = torch::empty({m, (long)H}, bopt);
   auto dhr = torch::empty({LIN ? 0 : m, (long)H}, bopt);
   auto dhc = torch::empty({LIN ? 0 : m, (long)H}, bopt);
   auto dcd = torch::empty({m, 3}, fopt);
@@ -759,14 +629,10 @@ static std::vector<torch::Tensor> fused_edge_backward_impl(
     dw3v = torch::zeros({(long)H}, fopt);
     gb = torch::zeros({3 * (long)H}, fopt);
   }
-  auto gw1 = torch::zeros({FUSE_WG ? (long)H : 0, (long)K_OUT}, fopt);
-  auto gw2 = torch::zeros({FUSE_WG ? (long)H : 0, (long)H}, fopt);
-  auto gw3 = torch::zeros({FUSE_WG ? (long)H : 0, (long)H}, fopt);
   if (m == 0) {
     if (LIN)
       return {t1, msg, dz1, dz2, dz3, dcd, dw3v, gb,
               torch::zeros({(long)H, 3}, fopt)};
-    if (FUSE_WG) return {dhr, dhc, dcd, dw3v, gb, gw1, gw2, gw3};
     return {ein, t1, msg, dz1, dz2, dz3, dhr, dhc, dcd, dw3v, gb};
   }
   auto stream = at::hip::getCurrentHIPStream();
@@ -828,17 +694,13 @@ static std::vector<torch::Tensor> fused_edge_backward_impl(
       reinterpret_cast<bf16*>(dhr.data_ptr()),
       reinterpret_cast<bf16*>(dhc.data_ptr()), dcd.data_ptr<float>(),
       dw3v.data_ptr<float>(), gb.data_ptr<float>(),
-      FUSE_WG ? gw1.data_ptr<float>()
-              : (LIN ? tail_part.data_ptr<float>() : nullptr),
-      FUSE_WG ? gw2.data_ptr<float>() : nullptr,
-      FUSE_WG ? gw3.data_ptr<float>() : nullptr, m, normalize ? 1 : 0,
+      LIN ? tail_part.data_ptr<float>() : nullptr, m, normalize ? 1 : 0,
       (float)eps);
   if (LIN) {
     // aten's sum is deterministic: a fixed fold over the partial rows
     auto gw1_tail = tail_part.sum(0).view({(long)H, 3});
     return {t1, msg, dz1, dz2, dz3, dcd, dw3v, gb, gw1_tail};
   }
-  if (FUSE_WG) return {dhr, dhc, dcd, dw3v, gb, gw1, gw2, gw3};
   return {ein, t1, msg, dz1, dz2, dz3, dhr, dhc, dcd, dw3v, gb};
 }
 
@@ -861,23 +723,6 @@ std::vector<torch::Tensor> fused_edge_backward(
         h, coord, eattr, row, col, dmsg_n, dtrans_n, w1, b1, w2, b2, w3,
         b3, w3v, normalize, eps, std::move(prepped));
   return fused_edge_backward_impl<64, EB_PLAIN>(
-      h, coord, eattr, row, col, dmsg_n, dtrans_n, w1, b1, w2, b2, w3, b3,
-      w3v, normalize, eps, std::move(prepped));
-}
-
-// wgrad-fused variant: returns {dhr, dhc, dcd, dw3v, gb, gw1, gw2, gw3} —
-// the three weight gradients come out of the kernel directly; no per-edge
-// intermediates are materialized.
-std::vector<torch::Tensor> fused_edge_backward_wg(
-    torch::Tensor h, torch::Tensor coord, torch::Tensor eattr,
-    torch::Tensor row, torch::Tensor col, torch::Tensor dmsg_n,
-    torch::Tensor dtrans_n, torch::Tensor w1, torch::Tensor b1,
-    torch::Tensor w2, torch::Tensor b2, torch::Tensor w3, torch::Tensor b3,
-    torch::Tensor w3v, bool normalize, double eps,
-    std::vector<torch::Tensor> prepped) {
-  TORCH_CHECK(h.size(1) == 64,
-              "the wgrad-fused edge backward is tuned for hidden_nf=64");
-  return fused_edge_backward_impl<64, EB_FUSE_WG>(
       h, coord, eattr, row, col, dmsg_n, dtrans_n, w1, b1, w2, b2, w3, b3,
       w3v, normalize, eps, std::move(prepped));
 }

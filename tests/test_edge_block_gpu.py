@@ -202,12 +202,11 @@ class _Case:
             self.h, self.bt.pos, self.bt.edge_attr, self.row, self.col,
             *self._weights(), self.normalize, EPS)
 
-    def backward(self, wg=False):
-        fn = (ops.hip_ext().fused_edge_backward_wg if wg
-              else ops.hip_ext().fused_edge_backward)
-        return fn(self.h, self.bt.pos, self.bt.edge_attr, self.row, self.col,
-                  self.dmsg_n, self.dtrans_n, *self._weights(),
-                  self.normalize, EPS)
+    def backward(self):
+        return ops.hip_ext().fused_edge_backward(
+            self.h, self.bt.pos, self.bt.edge_attr, self.row, self.col,
+            self.dmsg_n, self.dtrans_n, *self._weights(),
+            self.normalize, EPS)
 
 
 class _Ratios(dict):
@@ -419,21 +418,10 @@ class _Stages:
                 U23 * self.dn.abs()
                 * (4 * (self.H + 2) * hf["mag_p"] + 2 * hf["fx"]).unsqueeze(1))
 
-    def wgrads(self):
-        """dW = dz^T act over the emitted bf16 factors, which are the very
-        values the wgrad-fused kernel holds in LDS: M*u23*mag."""
-        out = {}
-        for name, dz, act in (("gw1", self.dz1, self.ein),
-                              ("gw2", self.dz2, self.t1),
-                              ("gw3", self.dz3, self.msg)):
-            a, b = dz.double(), act.double()
-            out[name] = (a.t() @ b, self.c.m * U23 * (a.abs().t() @ b.abs()))
-        return out
-
 
 def _check_plain(c, title):
     """Forward + plain backward of one case, every stage. Returns the
-    stages (for the wgrad-fused comparison) and the forward outputs."""
+    stages and the forward outputs."""
     H, K_IN = c.hdim, 2 * c.hdim + 3
     fwd_msg, fwd_trans = c.forward()
     outs = c.backward()
@@ -543,28 +531,7 @@ def test_edge_second_tile_trip_accumulators():
         assert bool((dz[~live] == 0).all())
 
 
-@pytest.mark.parametrize("normalize", [False, True])
-@pytest.mark.parametrize("m", [1, 65, 64 * 9 - 13])
-def test_edge_wgrad_fused_variant(m, normalize):
-    """fused_edge_backward_wg (opt-in, H = 64): node-side outputs under
-    the plain variant's bounds, weight gradients against dz^T act formed
-    from the plain variant's emitted tensors."""
-    c = _Case(graph_random(m, 24 if m < 128 else 97), 64, normalize)
-    st = _Stages(c, c.backward()).build()
-    dhr, dhc, dcd, dw3v, gb, gw1, gw2, gw3 = c.backward(wg=True)
-    R = _Ratios()
-    for tag, g in (("dhr", dhr), ("dhc", dhc), ("dcd", dcd),
-                   ("dw3v", dw3v), ("gb", gb)):
-        R.check(tag, g, *st.refs[tag])
-    wg = st.wgrads()
-    assert gw1.shape == (64, st.K_OUT)
-    for tag, g in (("gw1", gw1), ("gw2", gw2), ("gw3", gw3)):
-        assert g.dtype == torch.float32
-        R.check(tag, g, *wg[tag])
-    R.report(f"case=wg M={m} H=64 norm={int(normalize)}")
-
-
-@pytest.mark.parametrize("which", ["forward", "backward", "backward_wg"])
+@pytest.mark.parametrize("which", ["forward", "backward"])
 def test_direct_call_rejects_fp32_weights(which):
     """Without ``prepped`` the kernels read w1/w2/w3 as bf16; fp32 weights
     must raise instead of being reinterpreted."""
@@ -577,10 +544,8 @@ def test_direct_call_rejects_fp32_weights(which):
     with pytest.raises(RuntimeError, match="must be bf16"):
         if which == "forward":
             ext.fused_edge_forward(*geo, *tail)
-        elif which == "backward":
-            ext.fused_edge_backward(*geo, c.dmsg_n, c.dtrans_n, *tail)
         else:
-            ext.fused_edge_backward_wg(*geo, c.dmsg_n, c.dtrans_n, *tail)
+            ext.fused_edge_backward(*geo, c.dmsg_n, c.dtrans_n, *tail)
 
 
 # ------------------------------------------------- end to end (python glue)
