@@ -625,9 +625,9 @@ def _warn_fallback(op: str, reason: str):
     print(f"[distegnn_amd.ops] {op}: fused MFMA kernel not applicable "
           f"({reason}); running the eager composition instead — expect a "
           f"large per-step slowdown. The hand-written gfx950 kernels cover "
-          f"hidden_nf in {{32, 64, 128}} (the node block: {{32, 64}} in "
-          f"bf16, {{32, 64, 128}} in fp32, with node_attr_nf<=8 and a "
-          f"residual SiLU node_mlp of output width hidden_nf), "
+          f"hidden_nf in {{32, 64, 128}} (the node block with "
+          f"node_attr_nf<=8 and a residual SiLU node_mlp of output width "
+          f"hidden_nf), "
           f"edge_attr_nf=2, virtual_channels<=8, in bf16 (forward and "
           f"backward) and in fp32 when no gradient is needed (forward "
           f"only: fp32 evaluation under no_grad runs the edge, virtual and "
@@ -926,11 +926,12 @@ def eager_node_block(h, agg_e, agg_v, attr, node_mlp, vel_mlp, residual,
 
 
 class _FusedNodeBlockFn(torch.autograd.Function):
-    """Fused MFMA node block (csrc/fused_node.hip): phi_h with its residual
-    and phi_v in one kernel each way. Only the inputs are saved; the
-    backward kernel recomputes both pre-activations, emits the data
-    gradients and the three operands of the weight gradients, and sums the
-    bias / head / attribute-column gradients itself (per-wave partial rows,
+    """Fused MFMA node block (csrc/fused_node.hip, csrc/fused_node_h128.hip
+    at hidden_nf = 128): phi_h with its residual and phi_v in one kernel
+    each way. Only the inputs are saved; the backward kernel recomputes
+    both pre-activations, emits the data gradients and the three operands
+    of the weight gradients, and sums the bias / head / attribute-column
+    gradients itself (partial rows per wave, per block at hidden_nf = 128,
     folded here by one deterministic sum). The matrix gradients go through
     the split-K family."""
 
@@ -1000,7 +1001,7 @@ class _FusedNodeBlockFn(torch.autograd.Function):
                 gwv2, gbv2, None)
 
 
-_NODE_H = (32, 64)   # instantiations in csrc/fused_node.hip
+_NODE_H = (32, 64, 128)   # csrc/fused_node.hip; 128: csrc/fused_node_h128.hip
 _NODE_H_F32 = (32, 64, 128)   # instantiations in csrc/fused_node_f32.hip
 _NODE_MAX_ATTR = 8
 
@@ -1063,10 +1064,12 @@ def fused_node_block(h, agg_e, agg_v, attr, node_mlp, vel_mlp, residual=True,
 
     Dispatch, on GPU with node_attr_nf <= 8 and residual Linear-SiLU-Linear
     MLPs of output width hidden_nf, any N >= 0: the bf16 HIP kernel pair
-    (csrc/fused_node.hip, forward and backward) for bf16 h with hidden_nf in
-    {32, 64}; the forward-only fp32 kernel (csrc/fused_node_f32.hip) with
-    hidden_nf in {32, 64, 128} when h, agg_e, agg_v, attr and every
-    parameter are fp32 and no gradient is needed; the composition
+    (csrc/fused_node.hip, forward and backward; at hidden_nf = 128 the
+    variant of csrc/fused_node_h128.hip, which reads its weights from L2)
+    for bf16 h with hidden_nf in {32, 64, 128}; the forward-only fp32 kernel
+    (csrc/fused_node_f32.hip) with the same widths when h, agg_e, agg_v,
+    attr and every parameter are fp32 and no gradient is needed; the
+    composition
     (``eager_node_block``) otherwise, with one warning that names the
     reason. DISTEGNN_DISABLE_FUSED=1 and DISTEGNN_NODE_EAGER=1 opt out
     silently. phiv is fp32 from the kernels (``coord_update`` wants fp32),

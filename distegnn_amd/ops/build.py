@@ -29,6 +29,7 @@ SOURCES = [
     os.path.join(_CSRC, "fused_virtual.hip"),
     os.path.join(_CSRC, "fused_virtual_f32.hip"),
     os.path.join(_CSRC, "fused_node.hip"),
+    os.path.join(_CSRC, "fused_node_h128.hip"),
     os.path.join(_CSRC, "fused_node_f32.hip"),
     os.path.join(_CSRC, "elementwise.hip"),
     os.path.join(_CSRC, "cfconv.hip"),

@@ -24,11 +24,15 @@
 // Bias / head / attribute-column gradients are accumulated in registers
 // over the tiles a wave walks and written once per (block, wave) as a
 // partial row; the host folds the rows with one deterministic sum.
+//
+// Instantiated for H in {32, 64}. At H = 128 the weights do not fit in LDS;
+// the entry points below hand that width to fused_node_h128.hip.
 
 #include <ATen/hip/HIPContext.h>
 #include <torch/extension.h>
 
 #include "common.h"
+#include "fused_node_h128.h"
 
 namespace {
 
@@ -567,6 +571,12 @@ std::vector<torch::Tensor> fused_node_forward(
                         : torch::empty({n, (long)hd}, h.options());
   auto phiv = torch::empty({n, 1}, h.options().dtype(torch::kFloat));
   if (n == 0) return {h_out, phiv};
+  if (hd == 128) {  // weights read from L2: fused_node_h128.hip
+    TORCH_CHECK(a <= 8, "fused_node: node_attr_nf > 8");
+    fused_node_h128_forward(h, agg_e, agg_v, attr, a, prepped, vel_only,
+                            h_out, phiv);
+    return {h_out, phiv};
+  }
   auto stream = at::hip::getCurrentHIPStream();
   const bf16* attr_p = a > 0 ? bp(*attr) : nullptr;
 
@@ -609,7 +619,7 @@ std::vector<torch::Tensor> fused_node_forward(
   switch (hd) {
     NODE_FWD_H(32)
     NODE_FWD_H(64)
-    default: TORCH_CHECK(false, "fused_node: hidden_nf must be 32 or 64");
+    default: TORCH_CHECK(false, "fused_node: hidden_nf must be 32, 64 or 128");
   }
 #undef NODE_FWD_H
 #undef NODE_FWD_A
@@ -621,7 +631,7 @@ std::vector<torch::Tensor> fused_node_forward(
 // wv1^T, bv1, wv2. Returns dh, dagg_e, dagg_v, dz1, t1, dzv (bf16 [N,H];
 // only dh and dzv are filled in vel-only mode) and the fp32 partial rows
 // [blocks*4, 4H + H*A + 1] = gb1 | gb2 | gbv1 | gwv2 | dW1 attr columns |
-// gbv2, to be summed over dim 0.
+// gbv2, to be summed over dim 0 (one row per block at H = 128).
 std::vector<torch::Tensor> fused_node_backward(
     torch::Tensor dh_out, torch::Tensor dphiv, torch::Tensor h,
     torch::Tensor agg_e, torch::Tensor agg_v,
@@ -665,6 +675,13 @@ std::vector<torch::Tensor> fused_node_backward(
   torch::Tensor parts;
   if (n == 0) {
     parts = torch::zeros({0, pw}, opt.dtype(torch::kFloat));
+    return {dh, dagg_e, dagg_v, dz1, t1, dzv, parts};
+  }
+  if (hd == 128) {  // weights read from L2: fused_node_h128.hip
+    TORCH_CHECK(a <= 8, "fused_node: node_attr_nf > 8");
+    parts = fused_node_h128_backward(dh_out, dphiv, h, agg_e, agg_v, attr, a,
+                                     prepped, vel_only, dh, dagg_e, dagg_v,
+                                     dz1, t1, dzv);
     return {dh, dagg_e, dagg_v, dz1, t1, dzv, parts};
   }
   auto stream = at::hip::getCurrentHIPStream();
@@ -711,7 +728,7 @@ std::vector<torch::Tensor> fused_node_backward(
   switch (hd) {
     NODE_BWD_H(32)
     NODE_BWD_H(64)
-    default: TORCH_CHECK(false, "fused_node: hidden_nf must be 32 or 64");
+    default: TORCH_CHECK(false, "fused_node: hidden_nf must be 32, 64 or 128");
   }
 #undef NODE_BWD_H
 #undef NODE_BWD_A
