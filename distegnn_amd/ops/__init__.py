@@ -1132,7 +1132,9 @@ def fused_node_block(h, agg_e, agg_v, attr, node_mlp, vel_mlp, residual=True,
 
 
 def radius_graph(pos: torch.Tensor, r: float, loop: bool = False) -> torch.Tensor:
-    """Directed radius graph, row-sorted. GPU: HIP cell-list kernel."""
+    """Directed radius graph, row-sorted. GPU: HIP cell-list kernel
+    (``r == 0`` pairs up exact duplicates there as on the CPU; ``r < 0`` or
+    None is the full graph of ``reference.radius_graph``)."""
     if pos.is_cuda and r is not None and r >= 0:
         ext = _require_ext("radius_graph")
         if ext is not None:

@@ -207,14 +207,23 @@ torch::Tensor cfconv_forward(torch::Tensor xw1, torch::Tensor dist,
   TORCH_CHECK(f == 64 || f == 128, "fused cfconv supports F in {64,128}");
   long g = offsets.numel();
   TORCH_CHECK(g <= GPAD, "fused cfconv supports num_gaussians <= 64");
+  // the kernel reads both weights as bf16 bytes: an fp32 tensor here would
+  // be reinterpreted, not converted
+  TORCH_CHECK(w1f.is_cuda() && w1f.scalar_type() == torch::kBFloat16 &&
+                  w1f.dim() == 2 && w1f.size(0) == f && w1f.size(1) == GPAD,
+              "w1f must be CUDA bf16 [F][64] (gaussian dim zero-padded)");
+  TORCH_CHECK(w2f.is_cuda() && w2f.scalar_type() == torch::kBFloat16 &&
+                  w2f.dim() == 2 && w2f.size(0) == f && w2f.size(1) == f,
+              "w2f must be CUDA bf16 [F][F]");
+  TORCH_CHECK(b1.numel() == f && b2.numel() == f, "b1, b2 must be [F]");
   long m = row.numel();
+  TORCH_CHECK(dist.numel() == m && col.numel() == m,
+              "dist, row, col must have one entry per edge");
   auto msg = torch::empty({m, f}, xw1.options());
   if (m == 0) return msg;
   auto xc = xw1.contiguous();
   auto dc = dist.contiguous().to(torch::kFloat);
   auto w1c = w1f.contiguous();
-  TORCH_CHECK(w1c.size(1) == GPAD && w1c.size(0) == f,
-              "w1f must be [F][64] padded");
   auto w2c = w2f.contiguous();
   auto b1c = b1.contiguous().to(torch::kFloat);
   auto b2c = b2.contiguous().to(torch::kFloat);

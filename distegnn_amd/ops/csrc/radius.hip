@@ -7,9 +7,10 @@
 // the layout every downstream segment reduction expects.
 //
 // Pipeline (host orchestration in ext.cpp, device tensors throughout):
-//  1. bounding box + cell coords (torch ops), cell id per point
+//  1. bounding box (torch ops); cell id per point (cell_ids kernel)
 //  2. sort points by cell id (torch.sort), cell_start via searchsorted
-//  3. count_kernel: per point, scan the 27 neighbor cells, count hits
+//  3. count_kernel: per point, scan the cells within r of it (27 as a
+//     rule; the range comes from cell_axis, see radius_scan), count hits
 //  4. rowptr = cumsum(counts); allocate M (one host sync, unavoidable —
 //     output size is data-dependent; this op runs at data build time, and
 //     once per forward only for SchNet's interaction graph)
@@ -17,6 +18,9 @@
 
 #include <ATen/hip/HIPContext.h>
 #include <torch/extension.h>
+
+#include <algorithm>
+#include <cmath>
 
 #include "common.h"
 
@@ -28,16 +32,43 @@ struct GridSpec {
   int nx, ny, nz;     // cells per dim
 };
 
-__device__ __forceinline__ int cell_of(const GridSpec g, float x, float y,
-                                       float z) {
-  int ix = min(max((int)((x - g.ox) * g.inv_r), 0), g.nx - 1);
-  int iy = min(max((int)((y - g.oy) * g.inv_r), 0), g.ny - 1);
-  int iz = min(max((int)((z - g.oz) * g.inv_r), 0), g.nz - 1);
-  return (ix * g.ny + iy) * g.nz + iz;
+// THE cell coordinate of a point along one axis: binning (cell_ids) and the
+// scan range (radius_scan) both go through this one expression, so they
+// cannot disagree. Each step (fp32 subtract, fp32 multiply by inv_r > 0,
+// truncation, clamp) is monotone non-decreasing in x, hence so is the whole.
+__device__ __forceinline__ int cell_axis(float x, float o, float inv_r,
+                                         int nd) {
+  float t = (x - o) * inv_r;
+  // compare in float: t may exceed the int range (or be NaN) when the grid
+  // was capped far below extent / r
+  if (!(t > 0.f)) return 0;
+  if (t >= (float)(nd - 1)) return nd - 1;
+  return (int)t;
 }
 
-// For point i (in SORTED order so neighbors share cache lines), scan the 27
-// neighboring cells; count or fill. Templated to share the loop.
+__global__ void cell_ids(const float* __restrict__ pos, long* __restrict__ cid,
+                         GridSpec g, int n) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += gridDim.x * blockDim.x) {
+    int ix = cell_axis(pos[i * 3], g.ox, g.inv_r, g.nx);
+    int iy = cell_axis(pos[i * 3 + 1], g.oy, g.inv_r, g.ny);
+    int iz = cell_axis(pos[i * 3 + 2], g.oz, g.inv_r, g.nz);
+    cid[i] = ((long)ix * g.ny + iy) * g.nz + iz;
+  }
+}
+
+// For point i (in SORTED order so neighbors share cache lines), scan every
+// cell that can hold a neighbor; count or fill. Templated to share the loop.
+//
+// Scanned range, per axis: cell_axis(xi - rs) .. cell_axis(xi + rs), with
+// rs = fp32(r (1 + 2^-20)). The distance test below accepts j only if
+// |xi - xj| <= r (1 + 2^-22) (fp32 rounding of the difference, of the three
+// squares and their sum, and of r2), which is below rs; so
+// xi - rs <= xj <= xi + rs in exact arithmetic, fp32 rounding of xi -+ rs
+// is monotone and leaves the representable xj on the same side, and
+// cell_axis is monotone: cell(xj) lies in the range. "ix - 1 .. ix + 1"
+// does NOT have this property: the rounding error of (x - o) * inv_r grows
+// with the cell index, and a pair closer than r can land two cells apart.
 template <bool FILL>
 __global__ void radius_scan(const float* __restrict__ pos,      // [n,3] orig
                             const int* __restrict__ sorted_idx,  // [n]
@@ -45,36 +76,33 @@ __global__ void radius_scan(const float* __restrict__ pos,      // [n,3] orig
                             const long* __restrict__ rowptr,     // [n+1]
                             long* __restrict__ out_col,          // [m]
                             int* __restrict__ count,             // [n]
-                            GridSpec g, float r2, int n) {
+                            GridSpec g, float r2, float rs, int n) {
   for (int si = blockIdx.x * blockDim.x + threadIdx.x; si < n;
        si += gridDim.x * blockDim.x) {
     int i = sorted_idx[si];
     float xi = pos[i * 3], yi = pos[i * 3 + 1], zi = pos[i * 3 + 2];
-    int ix = min(max((int)((xi - g.ox) * g.inv_r), 0), g.nx - 1);
-    int iy = min(max((int)((yi - g.oy) * g.inv_r), 0), g.ny - 1);
-    int iz = min(max((int)((zi - g.oz) * g.inv_r), 0), g.nz - 1);
+    const int x0 = cell_axis(xi - rs, g.ox, g.inv_r, g.nx);
+    const int x1 = cell_axis(xi + rs, g.ox, g.inv_r, g.nx);
+    const int y0 = cell_axis(yi - rs, g.oy, g.inv_r, g.ny);
+    const int y1 = cell_axis(yi + rs, g.oy, g.inv_r, g.ny);
+    const int z0 = cell_axis(zi - rs, g.oz, g.inv_r, g.nz);
+    const int z1 = cell_axis(zi + rs, g.oz, g.inv_r, g.nz);
     int c = 0;
     long base = FILL ? rowptr[i] : 0;
-    for (int dx = -1; dx <= 1; ++dx) {
-      int jx = ix + dx;
-      if (jx < 0 || jx >= g.nx) continue;
-      for (int dy = -1; dy <= 1; ++dy) {
-        int jy = iy + dy;
-        if (jy < 0 || jy >= g.ny) continue;
-        for (int dz = -1; dz <= 1; ++dz) {
-          int jz = iz + dz;
-          if (jz < 0 || jz >= g.nz) continue;
-          int cell = (jx * g.ny + jy) * g.nz + jz;
-          for (int sj = cell_start[cell]; sj < cell_start[cell + 1]; ++sj) {
-            int j = sorted_idx[sj];
-            if (j == i) continue;
-            float ddx = xi - pos[j * 3];
-            float ddy = yi - pos[j * 3 + 1];
-            float ddz = zi - pos[j * 3 + 2];
-            if (ddx * ddx + ddy * ddy + ddz * ddz <= r2) {
-              if (FILL) out_col[base + c] = j;
-              ++c;
-            }
+    for (int jx = x0; jx <= x1; ++jx) {
+      for (int jy = y0; jy <= y1; ++jy) {
+        // cells jz = z0..z1 are adjacent in the table: one run of points
+        long cell = ((long)jx * g.ny + jy) * g.nz;
+        for (int sj = cell_start[cell + z0]; sj < cell_start[cell + z1 + 1];
+             ++sj) {
+          int j = sorted_idx[sj];
+          if (j == i) continue;
+          float ddx = xi - pos[j * 3];
+          float ddy = yi - pos[j * 3 + 1];
+          float ddz = zi - pos[j * 3 + 2];
+          if (ddx * ddx + ddy * ddy + ddz * ddz <= r2) {
+            if (FILL) out_col[base + c] = j;
+            ++c;
           }
         }
       }
@@ -90,6 +118,9 @@ std::tuple<torch::Tensor, torch::Tensor> radius_graph_gpu(torch::Tensor pos,
                                                           double r) {
   TORCH_CHECK(pos.is_cuda() && pos.dim() == 2 && pos.size(1) == 3,
               "pos must be [N,3] CUDA");
+  TORCH_CHECK(r >= 0 && std::isfinite(r),
+              "radius must be finite and >= 0, got ", r);
+  TORCH_CHECK(pos.size(0) < (1L << 29), "radius_graph indexes with int32");
   auto p = pos.contiguous().to(torch::kFloat);
   long n = p.size(0);
   auto lopt = p.options().dtype(torch::kLong);
@@ -108,10 +139,18 @@ std::tuple<torch::Tensor, torch::Tensor> radius_graph_gpu(torch::Tensor pos,
   const float* mx = pmax_h.data_ptr<float>();
   GridSpec g;
   g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
-  g.inv_r = (float)(1.0 / r);
+  // Cell edge: r, but never below 2^-20 of the longest extent, so that a
+  // tiny or zero r (r == 0 pairs up exact duplicates) forms neither 1/0
+  // nor a cell count beyond int. Any cell edge is correct: the scan range
+  // follows from r, not from the cell size.
+  double ext = std::max({(double)mx[0] - mn[0], (double)mx[1] - mn[1],
+                         (double)mx[2] - mn[2]});
+  double edge = std::max(r, ext * (1.0 / (1 << 20)));
+  if (!(edge > 0.0) || !std::isfinite((float)(1.0 / edge))) edge = 1.0;
+  g.inv_r = (float)(1.0 / edge);
   auto dim = [&](float lo, float hi) {
-    int d = (int)std::floor((hi - lo) / r) + 1;
-    return std::max(d, 1);
+    double d = std::floor(((double)hi - lo) / edge) + 1.0;
+    return (d >= 1.0) ? (int)std::min(d, (double)(1 << 21)) : 1;
   };
   g.nx = dim(mn[0], mx[0]); g.ny = dim(mn[1], mx[1]); g.nz = dim(mn[2], mx[2]);
   // cap the cell table at ~64M entries (degenerate r): fall back by
@@ -122,13 +161,11 @@ std::tuple<torch::Tensor, torch::Tensor> radius_graph_gpu(torch::Tensor pos,
   }
   long ncell = (long)g.nx * g.ny * g.nz;
 
-  // cell id per point + sort (torch device ops)
-  auto px = p.select(1, 0), py = p.select(1, 1), pz = p.select(1, 2);
-  auto to_idx = [&](torch::Tensor v, float o, int nd) {
-    return ((v - o) * g.inv_r).floor().clamp(0, nd - 1).to(torch::kLong);
-  };
-  auto cid = (to_idx(px, g.ox, g.nx) * g.ny + to_idx(py, g.oy, g.ny)) * g.nz
-             + to_idx(pz, g.oz, g.nz);
+  // cell id per point (the kernels' own cell_axis) + sort
+  int threads = 256;
+  auto cid = torch::empty({n}, lopt);
+  cell_ids<<<num_blocks(n, threads), threads, 0, stream>>>(
+      p.data_ptr<float>(), cid.data_ptr<long>(), g, (int)n);
   auto sorted = cid.sort();
   auto sorted_cid = std::get<0>(sorted);
   auto sorted_idx = std::get<1>(sorted).to(torch::kInt);
@@ -137,11 +174,11 @@ std::tuple<torch::Tensor, torch::Tensor> radius_graph_gpu(torch::Tensor pos,
 
   auto counts = torch::zeros({n}, iopt);
   float r2 = (float)(r * r);
-  int threads = 256;
+  float rs = (float)(r * (1.0 + 1.0 / (1 << 20)));
   radius_scan<false><<<num_blocks(n, threads), threads, 0, stream>>>(
       p.data_ptr<float>(), sorted_idx.data_ptr<int>(),
       cell_start.data_ptr<int>(), nullptr, nullptr,
-      counts.data_ptr<int>(), g, r2, (int)n);
+      counts.data_ptr<int>(), g, r2, rs, (int)n);
 
   auto rowptr = torch::zeros({n + 1}, lopt);
   rowptr.slice(0, 1, n + 1).copy_(counts.to(torch::kLong).cumsum(0));
@@ -151,7 +188,7 @@ std::tuple<torch::Tensor, torch::Tensor> radius_graph_gpu(torch::Tensor pos,
   radius_scan<true><<<num_blocks(n, threads), threads, 0, stream>>>(
       p.data_ptr<float>(), sorted_idx.data_ptr<int>(),
       cell_start.data_ptr<int>(), rowptr.data_ptr<long>(),
-      col.data_ptr<long>(), nullptr, g, r2, (int)n);
+      col.data_ptr<long>(), nullptr, g, r2, rs, (int)n);
 
   auto row = torch::repeat_interleave(
       torch::arange(n, lopt), rowptr.slice(0, 1, n + 1) - rowptr.slice(0, 0, n));
